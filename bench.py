@@ -2,7 +2,7 @@
 """bench.py -- the reference's headline metric on MI355X: train utterances/sec of the TASU alignment step
 (SenseVoiceSmall -> projector -> Qwen2.5-1.5B, text-only CPS recipe, bf16) at N GPUs of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -13,8 +13,11 @@ exact Qwen2.5-1.5B / projector geometry (no pretrained weights exist on the box)
 pass, whose result the reference throws away in text-only mode (Multitask/model/ps-slm.py:430-454 vs :459-468),
 is NOT executed (stated in config.workload).
 
-Prints ONE JSON line (rank 0) with `roofline` (MFMA GEMM kernel, timed live with HIP events on the launch
-stream) and, at N = 1, `cpu_baseline` (the oracle's CPU port timed on the host cores, bounded sample).
+A plain run sets up, warms up W steps, times K steps and prints ONE JSON line (rank 0): `value` (utterances/s) and
+`ms_per_step` of those K steps.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (inputs are
+seeded: the same arguments give the same inputs).  `--full` adds everything else to the line: `roofline` (MFMA GEMM kernel,
+timed live with HIP events on the launch stream), the decode leg, the sub-records of configs 4 / 5 and the other variants,
+the data path and, at N = 1, `cpu_baseline` (the oracle's CPU port timed on the host cores, bounded sample).
 """
 import argparse
 import json
@@ -430,8 +433,46 @@ def lora_flops_per_utt(geo, S, lp):
     return ext, rank
 
 
+DUMP_BUDGET_ELEMENTS = 12 << 20    # --dump-outputs: at most 48 MB of float32 in all (a fixed, seeded sample of larger outputs)
+
+
+def dump_arrays(out_dir, arrays):
+    """``arrays`` ({name: tensor}) -> ``out_dir/<name>.npy``, float64 for scalars and float32 otherwise.  When the arrays hold more
+    than DUMP_BUDGET_ELEMENTS elements in all, each is cut to its share of the budget: the same sorted, seeded indices into its
+    flattened form on every run (seed = CRC32 of the name), so two builds can be compared element for element."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(int(t.numel()) for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach()
+        n = int(a.numel())
+        keep = n if total <= DUMP_BUDGET_ELEMENTS else min(n, -(-n * DUMP_BUDGET_ELEMENTS // total))
+        if keep < n:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, keep, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        dtype = np.float64 if n == 1 else np.float32
+        np.save(os.path.join(out_dir, name + ".npy"), a.double().cpu().numpy().astype(dtype))
+
+
+def step_outputs(model, out, acc):
+    """What a caller of the training step receives after its last step: the loss, the accuracy, the trainable tensors as the optimizer
+    left them and the gradients it applied, under the reference's names."""
+    core = model.core
+    arrays = {"loss": out.loss.detach().reshape(1)}
+    if isinstance(acc, torch.Tensor) or (acc is not None and acc != -1):
+        arrays["accuracy"] = torch.as_tensor(acc, dtype=torch.float64).reshape(1)
+    arrays.update({"param." + k: v for k, v in model.state_dict().items()})
+    grads = {} if core.freeze_projector else core.projector_grads()
+    grads.update(core.lora_grads())
+    arrays.update({"grad." + k: v for k, v in grads.items()})
+    return arrays
+
+
 def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank, want_decode, device=None, ops=None,
-              variable=False, blank_biased=False, lora=False, force_exchange=False):
+              variable=False, blank_biased=False, lora=False, force_exchange=False, full=True, dump_dir=None):
     """One training workload (path: "text" = the text-only CPS recipe of configs 2/3/5, "audio" = config 4: 500 feature frames
     through the SenseVoice encoder, CTC posterior, PSD, projector, LLM).  Returns the fields of a bench record.
     ``device`` / ``ops``: tests/test_bench_cpu.py drives this function over gloo with the CPU operator double (the N > 1
@@ -510,11 +551,13 @@ def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank,
     step_no = [0]
     ahead = audio and not getattr(args, "no_encoder_ahead", False)
     ahead_hits = [0]
+    last_acc = [None]
 
     def step():
         b = batches[step_no[0] % len(batches)]
         step_no[0] += 1
         out, acc = engine(**b)
+        last_acc[0] = acc
         if ahead:                                       # the next batch's frozen encoder pass under this batch's decoder step
             ahead_hits[0] += bool(engine.prefetch(**batches[step_no[0] % len(batches)]))
         seen_shapes.add((engine._last_state.S, engine._last_state.Ra))
@@ -530,10 +573,12 @@ def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank,
     sync()
     # hipGraph replay cannot carry per-launch event pairs, so with graphs the GEMM launches are timed in a second,
     # eager pass over the same number of steps right after the timed region (same kernels, same shapes, same data).
-    timed.enabled = on_gpu and rank == 0 and not core.use_graphs
+    # Without ``full`` (a plain bench run) neither the GEMM timing nor the exposed all-reduce time is taken.
+    timed.enabled = full and on_gpu and rank == 0 and not core.use_graphs
     lib0 = getattr(core.ops, "lib", None)
     k_eager0 = int(lib0.tasu_gemm_launch_count()) if (timed.enabled and lib0 is not None) else None
-    engine.time_exchange = exchanging
+    exchanging_timed = exchanging and full
+    engine.time_exchange = exchanging_timed
     engine.exposed_events = []
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -546,13 +591,18 @@ def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank,
     if k_eager0 is not None:                            # eager launches: the GEMM kernel launches of the timed steps themselves
         timed.kernel_launches = (int(lib0.tasu_gemm_launch_count()) - k_eager0) // max(steps, 1)
     timed.enabled = False
-    exposed_ms = engine.exposed_ms() / max(steps, 1) if exchanging else 0.0
+    exposed_ms = engine.exposed_ms() / max(steps, 1) if exchanging_timed else 0.0
     engine.time_exchange = False
     if world > 1:
         t = torch.tensor([dt, exposed_ms], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, exposed_ms = float(t[0].item()), float(t[1].item())
-    if core.use_graphs:
+    if dump_dir is not None:
+        if rank == 0:                                   # the last timed step's outputs, before anything else runs on the model
+            dump_arrays(dump_dir, step_outputs(model, out, last_acc[0]))
+        if world > 1:
+            dist.barrier()                              # the other ranks wait for the dump: no later collective can overtake it
+    if full and core.use_graphs:
         # hipGraph replay cannot carry per-launch event pairs: one eager step records the step's GEMM calls (every rank takes
         # part: the step contains the gradient all-reduce), rank 0 then replays exactly those launches as a GEMM-only graph
         core.use_graphs = False
@@ -594,7 +644,7 @@ def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank,
         # rotating operands, gfx950 x2 fetch correction.  Only for the configuration those passes ran.
         traffic, traffic_src = None, None
         pmc = os.path.join(ROOT, "profiles", PMC_FILE)
-        if os.path.isfile(pmc) and model_name == "qwen2.5-1.5b" and B == 16 and not audio and not variable and core.lora is None:
+        if full and os.path.isfile(pmc) and model_name == "qwen2.5-1.5b" and B == 16 and not audio and not variable and core.lora is None:
             from ps_slm_amd._lib import gemm_source_hash
             rec_pmc = json.load(open(pmc))
             if rec_pmc.get("gemm_source_hash") == gemm_source_hash():     # the counters describe the kernels that just ran
@@ -656,14 +706,16 @@ def train_leg(args, model_name, path, B, steps, warmup, world, rank, local_rank,
                                        "whole_step_frac_at_survey_flops prices the same utterances/s at SURVEY 8d's algorithmic "
                                        "FLOPs, which count them"},
         }
-        if exchanging:
+        if not full:
+            del rec["roofline"]                         # (a plain run times no GEMM launches of its own)
+        if exchanging_timed:
             rec["collective"] = engine.comm_info()      # ranks = ncclCommCount of the communicator the exchange ran on
             rec["allreduce_exposed_ms"] = round(exposed_ms, 3)
             rec["allreduce_note"] = (f"per step, max over ranks: time the compute stream waited for gradient ranges in step() "
                                      f"(event pairs around every wait); bucket exchanged in {len(core.grad_ranges(engine.w1_chunks))} ranges.  Expected "
                                      f"on 8 xGMI-connected GPUs: ~0.35 ms (the last 51-MB row block of the Linear1 weight gradient at "
                                      f"the ~300 GB/s bus bandwidth RCCL reaches; the whole 218-MB bucket would be ~1.3 ms), DESIGN.md 6")
-        if on_gpu and (core.lora is not None or audio or exchanging):
+        if full and on_gpu and (core.lora is not None or audio or exchanging):
             rec["side_streams"] = stream_report(device)   # which hardware queue every overlap role got (ps_slm_amd/streams.py)
         if want_decode:
             rec["decode"] = decode_leg(core, raw, B, new_tokens=200 if model_name != "qwen2.5-7b" else 64)
@@ -711,7 +763,7 @@ def _brief(r):
     return out
 
 
-def compact_line(full, full_path="profiles/bench_r06_full.json"):
+def compact_line(full, full_path=None):
     """The ONE stdout line: the contract's top-level keys, ``roofline`` and ``cpu_baseline`` as plain numbers and short names, and
     ``digest`` (value / ms_per_step / roofline fractions of every sub-record) -- no prose, every string <= 120 characters, the whole
     line < STDOUT_LINE_LIMIT bytes.  The complete record (sub-record bodies, notes, sources) goes to stderr and to ``full_path``."""
@@ -726,10 +778,11 @@ def compact_line(full, full_path="profiles/bench_r06_full.json"):
                                         f"{cfg.get('per_gpu_batch')} utt/GPU x S={cfg.get('seq_len')}"),
                       "per_gpu_batch": cfg.get("per_gpu_batch"), "seq_len": cfg.get("seq_len"), "parallelism": cfg.get("parallelism"),
                       "final_loss": cfg.get("final_loss")}
-    roof = full.get("roofline") or {}
-    line["roofline"] = {k: _clip(roof[k]) for k in _ROOF_KEYS if k in roof}
-    if "kernel" in line["roofline"]:
-        line["roofline"]["kernel"] = "gemm_pp_kernel + gemm_pipe_kernel (all MFMA GEMM launches of the step)"
+    roof = full.get("roofline")
+    if isinstance(roof, dict):                          # (a plain run measures no roofline)
+        line["roofline"] = {k: _clip(roof[k]) for k in _ROOF_KEYS if k in roof}
+        if "kernel" in line["roofline"]:
+            line["roofline"]["kernel"] = "gemm_pp_kernel + gemm_pipe_kernel (all MFMA GEMM launches of the step)"
     cb = full.get("cpu_baseline")
     if isinstance(cb, dict):
         line["cpu_baseline"] = {"value": cb.get("value"), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
@@ -755,7 +808,8 @@ def compact_line(full, full_path="profiles/bench_r06_full.json"):
     line["digest"] = {k: v for k, v in digest.items() if v is not None}
     if "wall_seconds" in full:
         line["wall_seconds"] = full["wall_seconds"]
-    line["full_record"] = full_path
+    if full_path is not None:
+        line["full_record"] = full_path
     return line
 
 
@@ -771,16 +825,17 @@ def _short_sample(s):
 
 
 def emit(full, fd, full_path):
-    """Full record -> stderr + ``full_path`` (best effort); compact line (< STDOUT_LINE_LIMIT bytes, checked) -> the real stdout."""
+    """Full record -> stderr + ``full_path`` (best effort; None: no file); compact line (< STDOUT_LINE_LIMIT bytes, checked) -> the real stdout."""
     text = json.dumps(full)
     sys.stderr.write("FULL_RECORD " + text + "\n")
     sys.stderr.flush()
-    try:
-        os.makedirs(os.path.dirname(os.path.join(ROOT, full_path)), exist_ok=True)
-        with open(os.path.join(ROOT, full_path), "w") as f:
-            f.write(text + "\n")
-    except OSError:
-        pass
+    if full_path is not None:
+        try:
+            os.makedirs(os.path.dirname(os.path.join(ROOT, full_path)), exist_ok=True)
+            with open(os.path.join(ROOT, full_path), "w") as f:
+                f.write(text + "\n")
+        except OSError:
+            pass
     out = json.dumps(compact_line(full, full_path))
     if len(out.encode()) >= STDOUT_LINE_LIMIT:            # (cannot happen with the fixed key set; never print an unparsable line)
         slim = compact_line(full, full_path)
@@ -823,9 +878,15 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the config-4 (audio-SFT) and config-5 (Qwen2.5-7B) sub-records")
     ap.add_argument("--no-data-path", action="store_true",
                     help="skip the data_path sub-record (the training entrypoint on a generated 2048-utterance wav-in-ark corpus in tmpfs)")
-    ap.add_argument("--full-record", default="profiles/bench_r06_full.json",
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline (GEMM-only replay), decode leg, configs 4 / 5 and the other "
+                         "sub-records, data path, CPU baselines; a plain run only sets up, warms up and times --steps steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, accuracy, trainable tensors and their "
+                         "gradients; a fixed, seeded sample where large) as DIR/<name>.npy")
+    ap.add_argument("--full-record", default=None,
                     help="where the complete record (every sub-record's body and notes) is written, relative to the repo; stdout carries "
-                         "only the compact line")
+                         "only the compact line (default: profiles/bench_full.json with --full, no file otherwise)")
     args = ap.parse_args()
     if args.cpu_baseline_worker:
         return cpu_baseline_worker(args.cpu_baseline_worker)
@@ -855,12 +916,13 @@ def main():
         wall[name] = round(now - t_mark[0], 1)
         t_mark[0] = now
     main_rec = train_leg(args, args.model, args.path, args.batch, args.steps, args.warmup, world, rank, local_rank,
-                         want_decode=world == 1 and not args.no_decode and args.path == "text",
-                         blank_biased=args.blank_biased and args.path == "audio", lora=args.lora)
+                         want_decode=args.full and world == 1 and not args.no_decode and args.path == "text",
+                         blank_biased=args.blank_biased and args.path == "audio", lora=args.lora, full=args.full,
+                         dump_dir=args.dump_outputs)
     lap("headline" + ("+decode" if "decode" in main_rec else ""))
     extras = {}
     headline = args.model == "qwen2.5-1.5b" and args.path == "text" and not args.lora
-    if world == 1 and headline and not args.no_extra:
+    if args.full and world == 1 and headline and not args.no_extra:
         # BASELINE.json configs 4 and 5 as sub-records of the same line (shorter runs: their steps are 3-4x longer)
         extras["variable_S"] = train_leg(args, "qwen2.5-1.5b", "text", args.batch, 32, 24, 1, 0, local_rank, False, variable=True)
         lap("variable_S")
@@ -905,7 +967,7 @@ def main():
                 dist.destroy_process_group()
         lap("exchange_1rank")
     data_path = None
-    if world == 1 and headline and not args.no_extra and not args.no_data_path:
+    if args.full and world == 1 and headline and not args.no_extra and not args.no_data_path:
         # SURVEY 8f item 1 / VERDICT r4 item 5: the REAL data path next to the synthetic-input figures -- the training entrypoint
         # (ps_slm_amd.finetune_deepspeed.main: jsonl -> wav-in-ark read -> HIP fbank / LFR / CMVN -> collate -> dynamic batching ->
         # reader thread -> step, hipGraph replay) on 2048 generated 30-second utterances in tmpfs; second epoch's rate
@@ -947,14 +1009,14 @@ def main():
             line[name] = rec
         if data_path is not None:
             line["data_path"] = data_path
-        if world == 1 and not args.no_cpu_baseline and headline:
+        if args.full and world == 1 and not args.no_cpu_baseline and headline:
             line["cpu_baseline"] = cpu_baseline("train1")
             lap("cpu_baseline")
             side = cpu_baselines(["train16", "decode1", "decode16"], 400)
             line["cpu_baselines"] = {"train_B16": side["train16"], "decode_B1": side["decode1"], "decode_B16": side["decode16"]}
             lap("cpu_baselines_B16_decode")
         line["wall_seconds"] = wall                     # where this run's wall clock went (the timed regions are a small part of it)
-        emit(line, real_stdout, args.full_record)
+        emit(line, real_stdout, args.full_record or ("profiles/bench_full.json" if args.full else None))
     if world > 1:
         dist.destroy_process_group()
 

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def _worker(rank, world, port, ret):
+def _worker(rank, world, port, ret, dump_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
     torch.set_num_threads(2)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -24,7 +24,7 @@ def _worker(rank, world, port, ret):
         import bench
         from fake_ops import FakeOps
         args = SimpleNamespace(drop_prob=0.0, no_graphs=True)
-        rec = bench.train_leg(args, "mid", "text", 2, 2, 1, world, rank, 0, False, device="cpu", ops=FakeOps())
+        rec = bench.train_leg(args, "mid", "text", 2, 2, 1, world, rank, 0, False, device="cpu", ops=FakeOps(), dump_dir=dump_dir)
         lrec = bench.train_leg(args, "mid", "text", 2, 2, 1, world, rank, 0, False, device="cpu", ops=FakeOps(), lora=True)   # --lora at N > 1
         arec = bench.train_leg(args, "mid", "audio", 2, 2, 1, world, rank, 0, False, device="cpu", ops=FakeOps())              # --path audio at N > 1
         ret[rank] = rec
@@ -34,11 +34,11 @@ def _worker(rank, world, port, ret):
         dist.destroy_process_group()
 
 
-def test_train_leg_two_ranks_over_gloo():
+def test_train_leg_two_ranks_over_gloo(tmp_path):
     world, port = 2, free_port()
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, ret, str(tmp_path / "dump")), nprocs=world, join=True)
     r0, r1 = ret[0], ret[1]
     assert r1 is None                                              # only rank 0 builds the record
     assert r0["unit"] == "utterances/s" and r0["config"]["parallelism"] == "dp2" and r0["config"]["per_gpu_batch"] == 2
@@ -47,6 +47,8 @@ def test_train_leg_two_ranks_over_gloo():
     assert r0["allreduce_exposed_ms"] >= 0.0 and "Expected on 8 xGMI-connected GPUs" in r0["allreduce_note"]
     assert r0["roofline"]["bound"] == "mfma" and r0["config"]["seq_len"] == 256
     assert 0.0 < r0["config"]["final_loss"] < 20.0
+    # --dump-outputs at N > 1: rank 0 writes, the others wait for it at a barrier
+    assert {"loss.npy", "param.encoder_projector.ffn.0.weight.npy"} <= set(os.listdir(tmp_path / "dump"))
     # the use_peft recipe through the same bookkeeping: the adapters' ranges ride in the exchange, FLOPs include the rank columns
     l0 = ret[10]
     assert ret[11] is None and "LoRA recipe" in l0["config"]["workload"] and l0["config"]["parallelism"] == "dp2"
@@ -156,3 +158,31 @@ def test_stdout_line_of_a_multi_rank_record():
     line = _check_line(json.dumps(bench.compact_line(full)))
     assert line["n_gpus"] == 8 and line["collective"]["ranks"] == 8 and line["allreduce_exposed_ms"] == 0.41
     assert line["config"]["parallelism"] == "dp8" and "cpu_baseline" not in line
+
+
+def test_plain_leg_times_only_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """A plain run (full=False) returns the headline fields without a roofline, and --dump-outputs writes the last timed step's
+    loss, accuracy, trainable tensors and gradients: identical from run to run, a seeded sample when over the budget."""
+    import numpy as np
+
+    import bench
+    from fake_ops import FakeOps
+    monkeypatch.setattr(bench, "DUMP_BUDGET_ELEMENTS", 20000)        # the mid projector holds ~120k: the sampling path runs
+    args = SimpleNamespace(drop_prob=0.0, no_graphs=True)
+    recs = []
+    with torch.random.fork_rng():
+        for d in ("a", "b"):
+            recs.append(bench.train_leg(args, "mid", "text", 2, 3, 1, 1, 0, 0, False, device="cpu", ops=FakeOps(), full=False,
+                                        dump_dir=str(tmp_path / d)))
+    for rec in recs:
+        assert set(rec) == {"value", "unit", "ms_per_step", "config"} and rec["value"] == pytest.approx(2 / (rec["ms_per_step"] * 1e-3), rel=2e-3)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "accuracy.npy", "param.encoder_projector.ffn.0.weight.npy", "grad.encoder_projector.ffn.0.weight.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.size
+    assert total <= 20000 + len(names)
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(recs[0]["config"]["final_loss"], abs=1e-4)

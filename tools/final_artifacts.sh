@@ -7,7 +7,7 @@ timeout 600 $RP --stats -d $A/prof_decode7b -- python3 tools/bench_paths.py deco
 timeout 600 $RP --stats -d $A/prof_decode -- python3 tools/bench_paths.py decode 16 > $A/${R}_decode_under_rocprof.json 2> $A/prof_decode.err
 for p in decode decode7b; do f=$(find $A/prof_$p -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $A/${R}_${p}_kernel_stats.csv; done
 find $A -name "*kernel_trace.csv" -delete; find $A -name "*agent_info.csv" -delete
-t0=$(date +%s); timeout 1500 python bench.py > $A/bench_$R.json 2> $A/bench_$R.err; echo "bench.py wall seconds: $(( $(date +%s) - t0 ))" | tee $A/bench_${R}_wall.txt
+t0=$(date +%s); timeout 1500 python bench.py --full > $A/bench_$R.json 2> $A/bench_$R.err; echo "bench.py wall seconds: $(( $(date +%s) - t0 ))" | tee $A/bench_${R}_wall.txt
 python -c "
 import json; d=json.load(open('$A/bench_$R.json')); print(json.dumps(d['digest']))"
 timeout 600 python tools/ab_decode_7b.py 2>/dev/null | head -6 > $A/${R}_decode7b_ab.txt; cat $A/${R}_decode7b_ab.txt

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 16
+#define TASU_ABI_VERSION 17
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -718,6 +718,18 @@ int tasu_f32_embed_merge(const float* table, const float* proj, int ldp, const i
  * the mean loss's gradient, (softmax - onehot) * inv_count on labelled rows, 0 elsewhere and in the pad columns [V, ld).          */
 int tasu_f32_ce(const float* logits, int ld, const int32_t* shift_labels, int M, int V, float* row_loss, int32_t* row_hit,
                 int32_t* row_argmax, float* row_lse, float* dlogits, const float* inv_count, void* stream);
+
+/* fp32 cross-attention projector (EncoderProjectorCTCCA, Multitask/model/projector.py:111-126, `encoder_projector =
+ * "cross-attention"` with use_fp16 = false): for every row r < R and head h < H, with dh = D / H,
+ *   out[r, h*dh:(h+1)*dh] = softmax_v(q[r, h*dh:(h+1)*dh] . table[v, h*dh:(h+1)*dh] / denom) . table[:, h*dh:(h+1)*dh]
+ * over all V rows of table [V, D] (row pitch D; the LLM's input embedding table is keys and values).  denom = float(dh) ** 0.5, the
+ * scores are DIVIDED by it (projector.py:120).  Fused (csrc/f32_ca.hip): online softmax over LDS-staged key tiles on
+ * v_mfma_f32_16x16x4_f32, no [R, V] buffer; the V range is split over workgroups and a merge launch combines the splits in ascending
+ * order (deterministic).  dh % 16 == 0, dh <= 512; ldq, ldo >= D, ldq % 4 == 0; q, table and workspace 16-byte aligned;
+ * workspace_floats >= tasu_f32_ca_workspace_floats(R, V, D, H) (-1 for an invalid shape).  TASU_ERR_ARG before any launch.   */
+int tasu_f32_ca_attn(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, int R,
+                     float* workspace, int64_t workspace_floats, void* stream);
+int64_t tasu_f32_ca_workspace_floats(int R, int V, int D, int H);
 
 /* ------------------------------------------------------------------------------------------ fp32 training step (backward)
  * train_config.use_fp16 = false DURING TRAINING (the shipped recipe, Multitask/scripts/finetune_deespeed_sensevoice.sh:37: forward and

@@ -113,7 +113,7 @@ PROTOTYPES = {
     "tasu_embed_rows": [vp, vp, vp, i32, i32, vp],
     "tasu_decode_step_prologue": [vp, vp, vp, vp, vp, f32, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp],
 }
-RESTYPE_I64 = {"tasu_gemm_launch_count"}
+RESTYPE_I64 = {"tasu_gemm_launch_count", "tasu_f32_ca_workspace_floats"}
 PROTOTYPES.update({
     "tasu_scale_softmax_rows_bf16": [vp, vp, vp, i32, i32, i32, f32, vp],
     "tasu_softmax_bwd_rows_bf16": [vp, vp, vp, vp, i32, i32, i32, f32, vp],
@@ -150,6 +150,8 @@ PROTOTYPES.update({
     "tasu_f32_embed_merge": [vp, vp, i32, vp, vp, vp, i32, i32, vp],
     "tasu_f32_logprob_topk": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp],
     "tasu_f32_ce": [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "tasu_f32_ca_attn": [vp, i32, vp, i32, i32, i32, f32, vp, i32, i32, vp, i64, vp],
+    "tasu_f32_ca_workspace_floats": [i32, i32, i32, i32],
     # fp32 training step: backward kernels (csrc/fp32_train.hip)
     "tasu_f32_rmsnorm_bwd": [vp, vp, vp, vp, i32, i32, f32, i32, vp],
     "tasu_f32_swiglu_bwd": [vp, vp, vp, i32, i32, vp],
@@ -161,7 +163,7 @@ PROTOTYPES.update({
     "tasu_f32_attn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
 })
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

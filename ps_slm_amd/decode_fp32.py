@@ -3,9 +3,10 @@
 The reference decodes WITHOUT autocast on fp32 weights (Multitask/inference_batch.py:113-117,146: the model is built in fp32,
 ``model.eval()``, ``model.generate(**batch)``; Multitask/model/ps-slm.py:660-675 -> HF ``generate(inputs_embeds=..., num_beams=4)``),
 so its tokens are those of an fp32 forward pass.  The bf16 path (ps_slm_amd/decode.py) reproduces them only where rounding cannot
-matter; this path computes what the reference computes: fp32 projector (LayerNorm -> Linear -> SiLU -> Linear on the fp32 master
-weights), fp32 embeddings and residual stream, fp32 q|k|v / RoPE / attention / MLP on fp32 copies of the frozen Qwen2 weights, an
-fp32 KV cache, fp32 logits, log-softmax and top-k -- csrc/fp32.hip through the C-ABI (``tasu_f32_*``).  The beam search itself is the
+matter; this path computes what the reference computes: the fp32 projector on the master weights (project_fp32: linear-silu,
+linear, cov1d-linear, and cross-attention through the fused tasu_f32_ca_attn over the input embedding table), fp32 embeddings and
+residual stream, fp32 q|k|v / RoPE / attention / MLP on fp32 copies of the frozen Qwen2 weights (with use_peft: the merged
+W + s B A of ps_slm_amd.lora.merged_llm_f32, one accessor, weights_f32), an fp32 KV cache, fp32 logits, log-softmax and top-k -- csrc/fp32.hip through the C-ABI (``tasu_f32_*``).  The beam search itself is the
 same device-side bookkeeping as the bf16 path's (``tasu_beam_update``, the cache row index, ``DeviceBeam``), and a generated
 position is one hipGraph replay.  Nothing is rounded to bf16; sums run in another order than the reference's CPU BLAS (fp32 MFMA,
 K ascending, K-range slabs added in ascending order: deterministic).  The audio branch runs the frozen SenseVoice encoder, the CTC
@@ -37,25 +38,33 @@ def _fragments(model):
     1 KiB per wave instruction from them instead of 16 rows x 64 B), made at the first generate(): +5.3 GB at Qwen2.5-1.5B.
     ``TASU_F32_FRAGMENTS=0``: A/B runs on the row-major matrices (the same bits)."""
     import os
-    llm = model.llm
     if os.environ.get("TASU_F32_FRAGMENTS", "1") == "0" or not hasattr(model.ops, "f32_to_fragments"):
         return None
-    fr = llm.f32.get("frag")
+    f32 = weights_f32(model)
+    fr = f32.get("frag")
     if fr is None:
         ops, nws = model.ops, _gemm_ws(model).numel()
 
         def to(w):                                         # only what the streaming kernel will read (Qwen2.5-7B's down projection,
             N, K = w.shape                                 # K = 18944, has no K slice it serves: no copy)
             return ops.f32_to_fragments(w) if ops.lib.tasu_f32_gemm_streams(64, N, K, nws) == 1 else w
-        fr = llm.f32["frag"] = dict(layers=[dict(wgu=to(f["wgu"]), wd=to(f["wd"])) for f in llm.f32["layers"]], head=to(llm.f32["head"]))
+        # a merged LoRA set shares the base lm_head: its fragment copy is the base set's, or the one kept across adapter updates
+        base_fr = model.llm.f32.get("frag") if f32 is not model.llm.f32 else None
+        head = base_fr["head"] if base_fr is not None else f32.get("frag_head")
+        if head is None:
+            head = f32["frag_head"] = to(f32["head"])
+        fr = f32["frag"] = dict(layers=[dict(wgu=to(f["wgu"]), wd=to(f["wd"])) for f in f32["layers"]], head=head)
     return fr
 
 
 def project_fp32(model, st: StepState):
-    """EncoderProjectorLinearSiLU (Multitask/model/projector.py:128-151) in fp32 on the master weights: st.dev['y2_f32'] [Rap, D]."""
+    """The projector in fp32 on the master weights (``pr.view(pr.p, ...)``, the layout of the bf16 images): st.dev['y2_f32'] [Rap, D].
+    linear-silu (EncoderProjectorLinearSiLU, Multitask/model/projector.py:128-151): LayerNorm -> Linear -> SiLU -> Linear;
+    linear (EncoderProjectorConcat, :28-49): k consecutive frames as one row -> Linear -> ReLU -> Linear;
+    cov1d-linear (EncoderProjectorCov1d, :53-73): Conv1d(kernel = stride = k) as one GEMM over the k-frame rows -> ReLU -> Linear ->
+    ReLU -> Linear;  cross-attention (EncoderProjectorCTCCA, :104-126): Q = W_q(post), then tasu_f32_ca_attn over the fp32 input
+    embedding table."""
     ops, pr = model.ops, model.proj
-    if pr.kind != "linear-silu":
-        raise NotImplementedError(f"fp32 decode serves the shipped projector (linear-silu), not {pr.kind!r}")
     f32 = torch.float32
     Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
     if "post" not in st.dev:                                   # text branch: the pseudo-posterior rows (ps-slm.py:337-358)
@@ -63,14 +72,39 @@ def project_fp32(model, st: StepState):
         ops.posterior_build(st.dev["post_ids"], st.dev["post_alpha"], post, Fap, K)
         st.dev["post"] = post
     ws = _gemm_ws(model)
-    xn = model._buf("f32_proj_xn", (Fap, Kp), f32)
-    ops.layernorm_fwd(st.dev["post"], pr.view(pr.p, "norm.weight"), pr.view(pr.p, "norm.bias"), xn, None, None, Fap, K, model.geo.ln_eps)
-    h = model._buf("f32_proj_h", (Rap, Hb), f32)
-    ops.f32_gemm(xn, pr.view(pr.p, pr.n_w1), h, Rap, Hb, Kp, bias=pr.view(pr.p, pr.n_b1), act=1, ws=ws)
     y2 = model._buf("f32_proj_y2", (Rap, Do), f32)
+    if pr.is_ca:
+        geo = model.geo
+        q = model._buf("f32_ca_q", (Rap, Do), f32)
+        ops.f32_gemm(st.dev["post"], pr.view(pr.p, "W_q.weight"), q, Rap, Do, Kp, ws=ws)
+        cws = model._buf("f32_ca_ws", (ops.f32_ca_workspace_floats(Rap, geo.llm_vocab, Do, geo.ca_heads),), f32)
+        ops.f32_ca_attn(q, model.llm.embed, y2, Rap, geo.ca_heads, ws=cws)
+        st.dev["y2_f32"] = y2
+        return y2
+    if pr.has_norm:
+        x = model._buf("f32_proj_xn", (Fap, Kp), f32)
+        ops.layernorm_fwd(st.dev["post"], pr.view(pr.p, "norm.weight"), pr.view(pr.p, "norm.bias"), x, None, None, Fap, K, model.geo.ln_eps)
+    else:
+        x = st.dev["post"]                                     # linear / cov1d-linear: the posterior as it is
+    x = x.view(Rap, pr.k * Kp)                                 # k consecutive frames = one projector row (k = 1: linear-silu)
+    if pr.has_conv:
+        c0 = model._buf("f32_proj_c0", (Rap, Kp), f32)
+        ops.f32_gemm(x, pr.view(pr.p, "conv1d.weight"), c0, Rap, Kp, pr.k * Kp, bias=pr.view(pr.p, "conv1d.bias"), act=2, ws=ws)
+        x = c0
+    h = model._buf("f32_proj_h", (Rap, Hb), f32)
+    ops.f32_gemm(x, pr.view(pr.p, pr.n_w1), h, Rap, Hb, pr.kin * Kp, bias=pr.view(pr.p, pr.n_b1), act=1 if pr.has_norm else 2, ws=ws)
     ops.f32_gemm(h, pr.view(pr.p, pr.n_w2), y2, Rap, Do, Hb, bias=pr.view(pr.p, pr.n_b2), ws=ws)
     st.dev["y2_f32"] = y2
     return y2
+
+
+def weights_f32(model):
+    """The fp32 weight set of the decoder, {"layers": [{wqkv, bqkv, wo, wgu, wd}], "head"}: the frozen copies, or -- use_peft -- the
+    merged W + s B A of ps_slm_amd.lora.merged_llm_f32 (rebuilt when the adapters changed)."""
+    if model.lora is not None:
+        from .lora import merged_llm_f32
+        return merged_llm_f32(model)
+    return model.llm.f32
 
 
 def _layer_fp32(model, l, x, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, cache=None, ctx=0, frag=None):
@@ -79,7 +113,7 @@ def _layer_fp32(model, l, x, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, w
     _resid_rmsnorm, _swiglu): 9 launches per layer at <= 64 beam rows instead of 13."""
     ops, geo, llm = model.ops, model.geo, model.llm
     D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
-    f, w = llm.f32["layers"][l], llm.layers[l]
+    f, w = weights_f32(model)["layers"][l], llm.layers[l]
     next_norm = llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm
     kc_l, vc_l, slot = cache if cache is not None else (None, None, None)
     ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, cos_t, sin_t, rows, H, G, D, ws, kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
@@ -91,8 +125,6 @@ def _layer_fp32(model, l, x, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, w
 
 
 def _need_f32(model):
-    if model.lora is not None:
-        raise NotImplementedError("the fp32 path of a LoRA-adapted model is not built (the merged weights exist in bf16 only)")
     if not getattr(model.llm, "f32", None):
         raise RuntimeError("the fp32 path needs the fp32 copies of the LLM weights: build the model with train_config.use_fp16=false "
                            "(model_factory sets LLMWeights.keep_f32 before loading)")
@@ -153,7 +185,7 @@ def forward_fp32(model, st: StepState, compute_loss=True):
     buf, d = model._buf, st.dev
     ws = _gemm_ws(model)
     logits = buf("f32_logits_all", (M0, V), f32)
-    ops.f32_gemm(xn0, llm.f32["head"], logits, M0, V, D, ws=ws)
+    ops.f32_gemm(xn0, weights_f32(model)["head"], logits, M0, V, D, ws=ws)
     d.update(logits=logits)
     if not compute_loss:
         return
@@ -191,7 +223,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     buf, d = model._buf, st.dev
     ws = _gemm_ws(model)
     frag = _fragments(model)
-    head = llm.f32["head"] if frag is None else ops.f32_weight(frag["head"], M, ws)
+    head = weights_f32(model)["head"] if frag is None else ops.f32_weight(frag["head"], M, ws)
 
     # ---- KV cache (fp32) + the beam row index of the bf16 path
     kc = buf("f32_kc", (L, M * ctx * W), f32)
@@ -209,7 +241,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     x, xn = buf("f32_x", (M, D), f32), buf("f32_xn", (M, D), f32)
     logits = buf("f32_logits", (M, V), f32)
     ops.embed_rows(xn0, last_rows, xn, B, D)                    # the final-normed last prompt position of every utterance
-    ops.f32_gemm(xn, llm.f32["head"], logits, B, V, D, ws=ws)
+    ops.f32_gemm(xn, weights_f32(model)["head"], logits, B, V, D, ws=ws)
     tv, ti = buf("dec_topv", (M, K), f32), buf("dec_topi", (M, K), i32)
     bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid)
     model._last_beam = bs

@@ -21,6 +21,10 @@ flat fp32 bucket (master, grad, Adam m / v, bf16 image), a layer's tensors conti
 completes them (last layer first): AdamW stays one launch, the gradient exchange gets one range per span of layers.  Nothing
 of the forward is recomputed: the operands [x | us] and every member's dropped input are kept per layer.  Decode runs on merged
 weights (merged_llm).  DESIGN.md 4g has the measurements.
+
+use_fp16 = false: generate() and the eval-mode forward run on fp32 merged weights W_f32 + s B A (merged_llm_f32): +1x the decoder's
+fp32 layer weights, about 5 GB at Qwen2.5-1.5B, plus fragment-order copies of gate|up and down (~4.6 GB) at the first fp32 generate().
+The training step of an adapted model stays on the bf16 path above.
 """
 import math
 from dataclasses import dataclass
@@ -158,6 +162,7 @@ class LoraParams:
         self.version = 0                                   # bumped whenever the adapters change (load, optimizer step)
         self._table = None                                 # device table of tasu_lora_refresh, built on first use
         self._merged, self._merged_version = None, -1      # decode-time weights (merged_llm below)
+        self._merged32, self._merged32_version = None, -1  # fp32 decode / eval weights (merged_llm_f32 below)
 
     # ---- views
     def view(self, flat, l, t, which):
@@ -323,6 +328,53 @@ def merged_llm(model):
         model._dec_graphs.clear()
         model._dec_seen.clear()
     lp._merged, lp._merged_version = m, lp.version
+    return m
+
+
+def merged_llm_f32(model):
+    """fp32 weights of the adapted decoder for the fp32 arithmetic mode (use_fp16 = false: generate() and the eval-mode forward,
+    ps_slm_amd/decode_fp32.py), W' = W_f32 + s B A from the fp32 master adapters -- the reference's peft forward computes
+    base(x) + s B (A x) in fp32 (Multitask/inference_batch.py:113-117); the merge moves the sum by fp32 rounding only.  Each adapted
+    target is one tasu_f32_gemm_nt into its rows (lp.cols[t]) of the group matrix, base rows as ``resid``: A operand s B [out, r],
+    W operand A^T [in, r], r zero-padded to the GEMM's K granule (32).  bqkv, the norms, the embedding and the lm_head are the base
+    set's tensors; the base fp32 copies are never written.  +1x the decoder's fp32 layer weights (~5 GB at Qwen2.5-1.5B, plus the
+    fragment-order copies of gate|up and down at the first generate()).  Rebuilt in place when the adapters changed (lp.version):
+    the fragment-order copies and the captured decode graphs are dropped then, as merged_llm does."""
+    lp, base = model.lora, model.llm
+    f32b = base.f32
+    if not f32b or not f32b.get("layers"):
+        raise RuntimeError("the fp32 path needs the fp32 copies of the LLM weights: build the model with train_config.use_fp16=false")
+    m = lp._merged32
+    if m is not None and lp._merged32_version == lp.version and len(m["layers"]) == len(f32b["layers"]):
+        return m
+    ops, p, s = model.ops, lp.proj.p, float(lp.cfg.scaling)
+    r, rk = lp.r, rup(lp.r, 32)
+    f32 = torch.float32
+    first = m is None or len(m["layers"]) != len(f32b["layers"])
+    if first:
+        m = {"layers": [dict(wqkv=torch.empty_like(f["wqkv"]), bqkv=f["bqkv"], wo=torch.empty_like(f["wo"]), wgu=torch.empty_like(f["wgu"]),
+                             wd=torch.empty_like(f["wd"])) for f in f32b["layers"]], "head": f32b["head"]}
+    else:
+        fr = m.pop("frag", None)                           # fragment-order copies of the old W' (the shared lm_head's stay valid)
+        if fr is not None:
+            m["frag_head"] = fr["head"]
+        model._dec_graphs.clear()
+        model._dec_seen.clear()
+    tg = lp.cfg.target_modules
+    a_op = torch.zeros(max(lp.dims[t][1] for t in tg), rk, dtype=f32, device=p.device)     # s B of one target, rank columns padded
+    b_op = torch.zeros(max(lp.dims[t][0] for t in tg), rk, dtype=f32, device=p.device)     # A^T of one target
+    for l, (f, w) in enumerate(zip(f32b["layers"], m["layers"])):
+        for g, ts in GROUPS:
+            name = lp.wname[g]
+            w[name].copy_(f[name])                         # un-adapted members keep the base rows
+            for t in ts:
+                if t not in tg:
+                    continue
+                (i, o), c0 = lp.dims[t], lp.cols[t]
+                a_op[:o, :r].copy_(lp.view(p, l, t, "B")).mul_(s)
+                b_op[:i, :r].copy_(lp.view(p, l, t, "A").t())
+                ops.f32_gemm(a_op, b_op, w[name][c0:c0 + o], o, i, rk, resid=f[name][c0:c0 + o])
+    lp._merged32, lp._merged32_version = m, lp.version
     return m
 
 

@@ -444,6 +444,7 @@ class TasuModel:
         self._ws = {}
         self._pack = None               # UploadPack: the step's host -> device inputs (created on the first upload on a GPU)
         self.arith = "bf16"             # arithmetic of generate(): "bf16" (autocast semantics) or "fp32" (ps_slm_amd/decode_fp32.py)
+        self.arith_train = "bf16"       # arithmetic of the training step: "fp32" where ps_slm_amd/train_fp32.py serves the model
         self.training = True
         # hipGraph replay of the (shape-static) forward / backward launch sequences: ~700 launches per step collapse
         # into two graph launches.  Keyed by the shapes baked into kernel arguments; the first call of a key runs
@@ -687,7 +688,8 @@ class TasuModel:
         self._flush_uploads()
         st.dev["post"] = rows
         st.dev["psd_lens"] = new_lens
-        self._projector_from_posterior(st)
+        if not fp32:                                   # (the fp32 paths run their own fp32 projector on these rows)
+            self._projector_from_posterior(st)
         return st
 
     def _encoder_output(self, input_features, input_feature_length):

@@ -762,6 +762,21 @@ class HipOps:
         self._chk(self.lib.tasu_f32_ce(_p(logits), logits.stride(0), _p(labels), M, V, _p(row_loss), _p(row_hit), _p(row_argmax),
                                        _p(row_lse), _p(dlogits), _p(inv_count), self._stream()), "tasu_f32_ce")
 
+    def f32_ca_attn(self, q, table, out, R, H, ws=None):
+        """The cross-attention projector's attention in fp32 (tasu_f32_ca_attn): out[r, head h] = softmax(q_h table_h^T / sqrt(dh))
+        table_h over all V rows of ``table`` [V, D].  ``ws``: fp32 workspace of at least f32_ca_workspace_floats(R, V, D, H) floats
+        (allocated here when None)."""
+        V, D = table.shape
+        need = self.f32_ca_workspace_floats(R, V, D, H)
+        if ws is None:
+            ws = torch.empty(max(need, 1), device=table.device, dtype=torch.float32)
+        denom = float(D // H) ** 0.5
+        self._chk(self.lib.tasu_f32_ca_attn(_p(q), q.stride(0), _p(table), V, D, H, denom, _p(out), out.stride(0), R, _p(ws), ws.numel(),
+                                            self._stream()), "tasu_f32_ca_attn")
+
+    def f32_ca_workspace_floats(self, R, V, D, H):
+        return int(self.lib.tasu_f32_ca_workspace_floats(R, V, D, H))
+
     # fp32 training step: backward kernels (csrc/fp32_train.hip)
     def f32_rmsnorm_bwd(self, dy, x, w, dx, M, D, eps, accumulate):
         self._chk(self.lib.tasu_f32_rmsnorm_bwd(_p(dy), _p(x), _p(w), _p(dx), M, D, eps, int(accumulate), self._stream()), "tasu_f32_rmsnorm_bwd")

@@ -213,15 +213,29 @@ def model_factory(train_config, model_config, **kwargs):
         raise NotImplementedError("peft_ckpt (a peft adapter DIRECTORY, ps-slm.py:110-112): load the adapters from the training "
                                   "checkpoint with ckpt_path instead -- it holds them under the reference's own key names")
     fp32_mode = not train_config.get("use_fp16", False)
+    raw = not train_config.get("ctc_posterior", True)
+    use_peft = bool(train_config.get("use_peft", False))
+    # the training step in fp32 (ps_slm_amd/train_fp32.py) serves the linear-silu projector without adapters; generate() and the
+    # eval-mode forward in fp32 (ps_slm_amd/decode_fp32.py) serve every projector and LoRA on the CTC-posterior branch
+    f32_train_served = projector == "linear-silu" and not use_peft
+    f32_eval_served = f32_train_served or not raw
     if fp32_mode:
         # the reference computes in fp32 unless use_fp16 wraps the step in bf16 autocast (deepspeed_utils.py:160,205) and ALWAYS
-        # decodes in fp32 (inference_batch.py:113-117).  use_fp16 = false therefore selects the fp32 kernels for generate()
-        # (ps_slm_amd/decode_fp32.py), the eval-mode forward and the training step (ps_slm_amd/train_fp32.py); use_fp16 = true
-        # selects bf16 autocast semantics, the path the benchmarks measure
-        logger.warning("train_config.use_fp16 is false: the reference's fp32 arithmetic -- generate(), evaluation and the training step run on "
-                       "the fp32 kernels (correctness mode: the training step is ~10x slower than with use_fp16=true, which selects the "
-                       "bf16-autocast path the benchmarks measure); LoRA and the non-default projectors have the bf16 path only")
-    raw = not train_config.get("ctc_posterior", True)
+        # decodes in fp32 (inference_batch.py:113-117).  use_fp16 = false therefore selects the fp32 kernels for generate(), the
+        # eval-mode forward and -- where train_fp32.py serves the model -- the training step; use_fp16 = true selects bf16 autocast
+        # semantics, the path the benchmarks measure
+        what = f"{projector} projector" + (" with LoRA adapters" if use_peft else "") + (" on raw encoder features" if raw else "")
+        if f32_train_served:
+            logger.warning("train_config.use_fp16 is false: the reference's fp32 arithmetic -- generate(), evaluation and the training step "
+                           "of the %s run on the fp32 kernels (correctness mode: the training step is ~10x slower than with "
+                           "use_fp16=true, which selects the bf16-autocast path the benchmarks measure)", what)
+        elif f32_eval_served:
+            logger.warning("train_config.use_fp16 is false: generate() and evaluation of the %s run on the fp32 kernels (the reference's "
+                           "arithmetic); its training step runs on the bf16-autocast path (the fp32 training step serves the "
+                           "linear-silu projector without LoRA only)", what)
+        else:
+            logger.warning("train_config.use_fp16 is false: the %s has the bf16-autocast path only (generate(), evaluation and the "
+                           "training step); the fp32 kernels serve the CTC-posterior branch", what)
     if raw and projector == "cross-attention":
         raise NotImplementedError("ctc_posterior=false with the cross-attention projector: the reference's raw-feature branch "
                                   "(ps-slm.py:515-523) calls the projector with one argument, EncoderProjectorCTCCA needs two")
@@ -239,8 +253,9 @@ def model_factory(train_config, model_config, **kwargs):
         from ps_slm_amd.ops import HipOps     # raises if libtasu_hip.so is missing or there is no GPU: no fallback
         ops = HipOps()
     core = TasuModel(geo, ops, device, keep_logits=bool(kwargs.get("keep_logits", True)))
-    if fp32_mode and device != "cpu" and not str(device).startswith("cpu") and projector == "linear-silu" and not train_config.get("use_peft", False):
+    if fp32_mode and device != "cpu" and not str(device).startswith("cpu") and f32_eval_served:
         core.arith = "fp32"
+        core.arith_train = "fp32" if f32_train_served else "bf16"
         core.llm.keep_f32 = True                       # fp32 copies of the frozen weights next to the bf16 ones (before loading)
     llm_path = str(model_config.get("llm_path", ""))
     need_encoder = not train_config.get("gt_emb", False) or raw or bool(kwargs.get("with_encoder", False))
@@ -474,7 +489,7 @@ class slam_model_asr:
         # use_fp16 = false outside training: the reference's fp32 arithmetic (evaluation(), deepspeed_utils.py:394-498, or any
         # model(**batch) under no autocast) -- fp32 projector / encoder / decoder / logits / CE (ps_slm_amd/decode_fp32.py)
         fp32_eval = core.arith == "fp32" and not self.training
-        fp32_train = core.arith == "fp32" and self.training and labels is not None      # the shipped recipe trains in fp32 too (train_fp32.py)
+        fp32_train = core.arith_train == "fp32" and self.training and labels is not None   # the shipped recipe trains in fp32 too (train_fp32.py)
         if self.gt_emb:
             ids_list = [self.encoder_tokenizer.encode(t) for t in GT]
             alphas = keeps = row_alphas = None

@@ -520,7 +520,7 @@ def bf16_ulp_jitter(seed, prob=0.15):
 
 def beam_search_generate(W, emb, mask, geo, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
                          eos_token_id=None, pad_token_id=None, mode="fp32", logit_jitter=None, logits_trace=None,
-                         logits_replay=None, kv_cache=False, step_times=None):
+                         logits_replay=None, kv_cache=False, step_times=None, margins=None):
     """slam_model_asr.generate's decode loop (Multitask/model/ps-slm.py:660-675): HF ``generate(inputs_embeds=...,
     num_beams=4, do_sample=False, early_stopping=False)`` restated (transformers generation/utils.py ``_beam_search``,
     un-vendored dependency): every step keeps the 2*num_beams best continuations, the first num_beams non-finished
@@ -538,7 +538,9 @@ def beam_search_generate(W, emb, mask, geo, num_beams=4, max_new_tokens=200, min
     (logits, running prefixes); ``logits_replay`` (such a list) replaces the network: a step whose running prefixes equal the
     recorded ones reuses the recorded logits (the network is a function of the prefixes), any other step ends the call with
     ``None`` -- a jittered run over a recorded trajectory therefore costs only the bookkeeping, and a run that leaves the
-    trajectory has already shown the case to be unstable."""
+    trajectory has already shown the case to be unstable.  ``margins`` (a list) receives, per step, every still-searching
+    utterance's smallest gap between consecutive scores of its 2 * num_beams + 1 best continuations: the closest decision of
+    that step (a tensor [B], +inf where the utterance is done)."""
     B, S, D = emb.shape
     nb, V = num_beams, lm_head_weight(W).shape[0]
     # HF counts ``min_length`` INCLUDING the prompt, and under ``inputs_embeds`` subtracts the embedded prompt's length from it
@@ -600,6 +602,9 @@ def beam_search_generate(W, emb, mask, geo, num_beams=4, max_new_tokens=200, min
         if cur < min_length:
             logp[:, eos] = float("-inf")
         acc = (logp.view(B, nb, V) + run_scores[:, :, None]).view(B, nb * V)
+        if margins is not None:
+            tv = torch.topk(acc, K + 1)[0]
+            margins.append(torch.where(unsat[:, 0], (tv[:, :-1] - tv[:, 1:]).min(1)[0], torch.full((B,), float("inf"), dtype=tv.dtype)))
         top_lp, top_ix = torch.topk(acc, K)
         beam_ix, tok = top_ix // V, top_ix % V
         cand = torch.gather(run_seq, 1, beam_ix[:, :, None].expand(-1, -1, max_new_tokens)).clone()

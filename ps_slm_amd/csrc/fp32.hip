@@ -994,10 +994,12 @@ __global__ __launch_bounds__(256) void f32_topk_merge_kernel(const float* __rest
 // Shifted cross entropy of one fp32 logits row per 1024-thread block (the eval-mode forward in fp32: loss_utils' CE over the rows
 // whose shifted label is >= 0, ignore_index -100): lse = max + log(sum exp(x - max)), row_loss = lse - x[label], row_hit =
 // (argmax == label), argmax ties -> the first column (torch.argmax).  Rows without a label: loss 0, hit 0 (lse / argmax still written).
-__global__ __launch_bounds__(1024) void f32_ce_kernel(const float* __restrict__ logits, int ld, const int32_t* __restrict__ labels, int V,
+// dlogits may alias logits (the fp32 training step writes the gradient over its logits): the two carry no __restrict__, and the
+// label's logit is read before a barrier that every thread passes before the first gradient store.
+__global__ __launch_bounds__(1024) void f32_ce_kernel(const float* logits, int ld, const int32_t* __restrict__ labels, int V,
                                                       float* __restrict__ row_loss, int32_t* __restrict__ row_hit,
                                                       int32_t* __restrict__ row_argmax, float* __restrict__ row_lse,
-                                                      float* __restrict__ dlogits, const float* __restrict__ inv_count) {
+                                                      float* dlogits, const float* __restrict__ inv_count) {
   __shared__ float red[16];
   __shared__ float bv[16];
   __shared__ int bi[16];
@@ -1024,22 +1026,20 @@ __global__ __launch_bounds__(1024) void f32_ce_kernel(const float* __restrict__ 
   float s = 0.f;
   for (int c = t; c < V; c += 1024) s += expf(x[c] - best);
   s = block_sum<16>(s, red);
+  const float lse = best + logf(s);
+  const int lab = labels[m];
+  const bool on = lab >= 0 && lab < V;
   if (t == 0) {
-    const float lse = best + logf(s);
-    const int lab = labels[m];
-    const bool on = lab >= 0 && lab < V;
     row_loss[m] = on ? lse - x[lab] : 0.f;
     row_hit[m] = on && bid == lab ? 1 : 0;
     if (row_argmax) row_argmax[m] = bid;
     if (row_lse) row_lse[m] = lse;
   }
   if (dlogits) {                                     // d(mean CE) / d logits = (softmax - onehot) / count on labelled rows, 0 elsewhere
-    const float lse = best + logf(s);
-    const int lab = labels[m];
-    const bool on = lab >= 0 && lab < V;
+    __syncthreads();                                 // (thread 0 has read x[lab]: in place, the stores below overwrite it)
     const float k = on ? inv_count[0] : 0.f;
     float* d = dlogits + (size_t)m * ld;
-    for (int c = t; c < ld; c += 1024) d[c] = c < V ? k * (expf(x[c] - lse) - (c == lab ? 1.f : 0.f)) : 0.f;   // (may alias the logits: own row, own columns)
+    for (int c = t; c < ld; c += 1024) d[c] = c < V ? k * (expf(x[c] - lse) - (c == lab ? 1.f : 0.f)) : 0.f;   // (own row, own columns)
   }
 }
 

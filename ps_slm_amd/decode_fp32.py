@@ -29,7 +29,9 @@ F32_MAX_CTX = 2048          # tasu_f32_attn_*: keys per query row
 
 def _gemm_ws(model):
     """The fp32 GEMMs' slab workspace: 16 K-range slabs of the widest narrow projection, or the lm_head's two slabs at 64 beam rows
-    (csrc/fp32.hip f32_stream_plan: a problem whose slabs do not fit runs unsplit on the tile kernel)."""
+    (csrc/fp32.hip f32_stream_plan: a problem whose slabs do not fit runs unsplit on the tile kernel).  EVERY fp32 caller (decode,
+    eval forward, training step, fp32 encoder) takes it from here: the K-split plans depend on its size, so one size from the first
+    fp32 call on keeps a product's bits, and the captured graphs, independent of which fp32 path ran first."""
     return model._buf("f32_gemm_ws", (max(16 * 128 * 4096, 2 * 64 * model.geo.llm_vocab),), torch.float32)
 
 

@@ -208,7 +208,8 @@ def encoder_posterior_fp32(model, feats, feat_lens):
     x0[:, 4:].copy_(feats.to(dev, f32, non_blocking=True))
     lens_h = (np.asarray(feat_lens.cpu() if isinstance(feat_lens, torch.Tensor) else feat_lens).astype(np.int64) + 4)
     lens = model._upload("enc_lens", lens_h.astype(np.int32))
-    ws = buf("f32_gemm_ws", (16 * 128 * 4096,), f32)
+    from .decode_fp32 import _gemm_ws
+    ws = _gemm_ws(model)                     # (one size for every fp32 caller: the workspace and the K-split plans never change)
     x = buf("enc_x", (M, Fd), f32)
     ops.sinusoid_pe(x0.view(M, Fd), x, B, Te, Fd, float(E) ** 0.5)
     qkv = buf("f32_enc_qkv", (M, 3 * E), f32)

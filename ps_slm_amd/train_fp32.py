@@ -18,7 +18,7 @@ frozen (dgrad only), like the bf16 step; LoRA and the non-default projectors tra
 import numpy as np
 import torch
 
-from .decode_fp32 import F32_MAX_CTX, _need_f32
+from .decode_fp32 import F32_MAX_CTX, _gemm_ws, _need_f32
 from .model import HD, StepState, rup
 
 
@@ -54,7 +54,7 @@ def forward_train_fp32(model, st: StepState):
     scale = HD ** -0.5
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
-    ws = buf("f32_gemm_ws", (16 * 128 * 4096,), f32)
+    ws = _gemm_ws(model)
     # ---- projector (EncoderProjectorLinearSiLU, projector.py:128-151) with its intermediates kept
     Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
     if "post" not in d:
@@ -114,7 +114,7 @@ def backward_fp32(model, st: StepState, on_ready=None):
     a = d["f32t"]
     xs, qkvs, aos, gus = a["xs"], a["qkvs"], a["aos"], a["gus"]
     wt = _transposed_weights(model)
-    ws = buf("f32_gemm_ws", (16 * 128 * 4096,), f32)
+    ws = _gemm_ws(model)
     dx, dn = buf("f32t_dx", (M, D), f32), buf("f32t_dn", (M, D), f32)
     dact, dgu = buf("f32t_dact", (M, I), f32), buf("f32t_dgu", (M, 2 * I), f32)
     dao, dqkv = buf("f32t_dao", (M, H * HD), f32), buf("f32t_dqkv", (M, LDQ), f32)

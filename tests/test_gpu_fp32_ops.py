@@ -515,3 +515,62 @@ def test_ce_gradient_fp32(ops):
     torch.cuda.synchronize()
     assert close(buf[:, :V], gx, 1e-5) and float(buf[:, V:].abs().sum()) == 0.0
     assert abs(float(row_loss.sum()) / n - float(loss)) < 1e-5 and float(buf[1].abs().sum()) == 0.0
+
+
+@pytest.mark.parametrize("M,V", [(512, 151936), (300, 152064), (512, 1000)])
+def test_ce_in_place_at_vocabulary_widths(ops, M, V):
+    """tasu_f32_ce with dlogits ALIASING the logits, as the fp32 training step calls it (train_fp32.py), at the Qwen2.5 vocabularies:
+    row_loss, row_lse, row_hit, row_argmax (the first maximum wins) and the gradient against float64, on labels -100, out of range
+    (V, negative), column 0, column V - 1, a label that ties the row maximum after its first occurrence and one that IS the first
+    occurrence -- and every output bit-identical to the call with a separate dlogits buffer."""
+    ld = (V + 63) // 64 * 64
+    g = torch.Generator(device="cuda").manual_seed(V + M)
+    logits = torch.randn(M, ld, generator=g, device="cuda") * 3.0
+    labels = torch.randint(0, V, (M,), generator=g, device="cuda").to(torch.int32)
+    edge = [-100, V, -7, 0, V - 1]
+    labels[: len(edge)] = torch.tensor(edge, dtype=torch.int32)
+    top = float(logits[:, :V].max()) + 2.0
+    logits[5, 17] = logits[5, V // 2] = top            # a tie of the row maximum: the label is its SECOND occurrence (no hit)
+    labels[5] = V // 2
+    logits[6, 40] = logits[6, V - 1] = top             # the label is its FIRST occurrence (hit)
+    labels[6] = 40
+    logits[7, V - 1] = top                             # the maximum in the last column, labelled
+    labels[7] = V - 1
+    logits[8, 0] = top                                 # the maximum in column 0, unlabelled
+    labels[8] = -100
+    on = (labels >= 0) & (labels < V)
+    inv = torch.tensor([1.0 / int(on.sum())], device="cuda")
+
+    def run(in_place):
+        buf = logits.clone()
+        d = buf if in_place else torch.full_like(buf, float("nan"))
+        out = (torch.empty(M, device="cuda"), torch.empty(M, dtype=torch.int32, device="cuda"),
+               torch.empty(M, dtype=torch.int32, device="cuda"), torch.empty(M, device="cuda"))
+        ops.f32_ce(buf, labels, M, V, out[0], out[1], out[2], out[3], dlogits=d, inv_count=inv)
+        torch.cuda.synchronize()
+        return out + (d,)
+
+    loss, hit, arg, lse, grad = run(True)
+    sep = run(False)
+    for a, b in zip((loss, hit, arg, lse, grad), sep):
+        assert torch.equal(a, b)
+    # float64 reference
+    x = logits[:, :V].double()
+    lse64 = torch.logsumexp(x, -1)
+    arg_ref = torch.argmax(logits[:, :V], -1)          # (torch.argmax: the first maximal value)
+    assert int(arg_ref[5]) == 17 and int(arg_ref[6]) == 40 and int(arg_ref[7]) == V - 1 and int(arg_ref[8]) == 0
+    lab = labels.long().clamp(0, V - 1)
+    loss64 = torch.where(on, lse64 - x.gather(1, lab[:, None])[:, 0], torch.zeros_like(lse64))
+    assert torch.equal(arg.long(), arg_ref)
+    assert torch.equal(hit.bool(), on & (arg_ref == labels.long()))
+    assert hit[5] == 0 and hit[6] == 1 and hit[7] == 1 and hit[8] == 0
+    assert float((lse.double() - lse64).abs().max()) < 1e-5 * float(lse64.abs().max())
+    assert float((loss.double() - loss64).abs().max()) < 1e-5 * float(lse64.abs().max())
+    assert float(loss[~on].abs().sum()) == 0.0
+    p = torch.softmax(x, -1)
+    g64 = (p - torch.nn.functional.one_hot(lab, V).double()) * on[:, None].double() / float(on.sum())
+    # per element: 1e-5 relative, plus a few fp32 ulps of the row's lse (p - 1 cancels on a label that holds most of the mass)
+    tol = 1e-5 * g64.abs() + (float(inv) * lse64.abs() * 2.0 ** -21)[:, None]
+    err = (grad[:, :V].double() - g64).abs()
+    assert bool((err <= tol).all()), float((err / tol).max())
+    assert float(grad[~on].abs().sum()) == 0.0 and float(grad[:, V:].abs().sum()) == 0.0

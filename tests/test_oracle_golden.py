@@ -221,6 +221,33 @@ def test_mid_audio_fp32():
     check_mid(out, grads, z, 1e-5)
 
 
+@pytest.mark.parametrize("name", ["qwen15_geo", "qwen7_geo"])
+def test_qwen_geometry_fixture_fp32(name):
+    """tests/golden/qwen15_geo.npz / qwen7_geo.npz (the REAL reference at the Qwen2.5-1.5B / 7B head and vocabulary geometry,
+    oracle/make_golden_qwen_geometry.py) are self-consistent: the oracle in fp32 on the weights and batch regenerated from the
+    stored seeds reproduces the merged mask, loss, accuracy, log-sum-exp and every stored logit (seeded, label and argmax columns)."""
+    import dataclasses
+
+    from qwen_geometry_cases import geometry, state_dict, text_batch
+    z = load_npz(name)
+    geo = geometry(name)
+    sd = state_dict(geo, int(z["seed_w"]))
+    batch = text_batch(geo, int(z["seed_b"]))
+    with torch.no_grad():
+        out = O.forward_text(sd, batch, dataclasses.asdict(geo), "fp32")
+    del sd
+    valid = out["mask"].bool()
+    assert torch.equal(valid, torch.from_numpy(z["merged_mask"]).bool())
+    close(out["loss"], z["loss"], rtol=1e-5, atol=1e-5)
+    close(out["acc"], z["acc"], rtol=0, atol=1e-6)
+    lg = out["logits"]
+    close(lg[:, :, torch.from_numpy(z["cols"])][valid], torch.from_numpy(z["logits_cols"])[valid], rtol=2e-4, atol=2e-4)
+    for col, key in (("label_col", "logits_label"), ("argmax", "logits_argmax")):
+        got = lg.gather(-1, torch.from_numpy(z[col]).long()[..., None])[..., 0]
+        close(got[valid], torch.from_numpy(z[key])[valid], rtol=2e-4, atol=2e-4)
+    close(torch.logsumexp(lg, -1)[valid], torch.from_numpy(z["lse"])[valid], rtol=2e-4, atol=2e-4)
+
+
 def test_mid_audio_psd_fp32():
     import dataclasses
     from conftest import mid_audio_psd_case

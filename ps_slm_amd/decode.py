@@ -19,7 +19,6 @@ import torch
 from .model import HD, StepState, rup
 
 NEG = -1.0e9
-DECODE_GRAPH_CACHE = 8   # decode-step graphs kept per model (LRU)
 BEAM_MAX_NB, BEAM_MAX_B, DECODE_MAX_CTX = 5, 256, 2048   # limits of tasu_beam_update / tasu_decode_step_prologue / tasu_attn_decode
 
 
@@ -123,6 +122,7 @@ class DeviceBeam:
                 model._done_host = torch.zeros(1, dtype=i32).pin_memory()
             self.done_host = model._done_host
             self.done_host.zero_()
+        model._last_beam = self                                            # (tests read the final scores / back-pointers)
 
     def result(self, pad):
         """Walks the back-pointers of every utterance's best finished hypothesis -> LongTensor [B, n_new] (CPU)."""
@@ -156,6 +156,69 @@ def effective_min_length(min_length, S):
     return max(int(min_length) - int(S), 0)
 
 
+def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention):
+    """Checks a generate() call against the limits of the device beam search (tasu_beam_update, tasu_decode_step_prologue:
+    include/tasu_hip.h) and the context limit ``max_ctx`` of the caller's cache attention, BEFORE any prefill.  Returns
+    (min_length in generated positions, eos, pad)."""
+    B, S = st.B, st.S
+    if not 1 <= nb <= BEAM_MAX_NB:
+        raise ValueError(f"num_beams={nb}: the device beam search serves 1..{BEAM_MAX_NB} beams")
+    if B > BEAM_MAX_B:
+        raise ValueError(f"{B} utterances per generate() call: the device beam search serves at most {BEAM_MAX_B}")
+    if max_new_tokens < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    if S + max_new_tokens > max_ctx:
+        raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds {attention} context limit {max_ctx}")
+    eos = model.geo.eos_id if eos_token_id is None else eos_token_id
+    pad = eos if pad_token_id is None else pad_token_id
+    return effective_min_length(min_length, S), eos, pad
+
+
+def kv_row_index(model, B, nb, S, ctx):
+    """The beam row index of the KV cache and the copy a beam reorder goes through (include/tasu_hip.h): the prompt is stored once
+    per utterance and a beam reorder permutes 4-byte index entries once per step instead of copying K/V in every layer."""
+    index = model._buf("dec_index", (B * nb, ctx), torch.int32)
+    index_tmp = model._buf("dec_index_tmp", (B * nb, ctx), torch.int32)
+    model.ops.kv_index_init(index, B, nb, S, ctx)
+    model.ops.kv_index_init(index_tmp, B, nb, S, ctx)
+    return index, index_tmp
+
+
+def prompt_rows(model, B, S, nb, valid):
+    """The first key of every beam row (left padding is at the front) and the row of every utterance's last prompt position, in
+    one copy.  ``valid``: real tokens per prompt."""
+    kstart = model._upload("dec_kstart", np.repeat(S - valid, nb).astype(np.int32), flush=False)
+    return kstart, model._upload("dec_last_rows", (np.arange(B, dtype=np.int32) + 1) * S - 1)
+
+
+def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
+    """Generated positions 2 .. max_new of a generate() call (``device_step``: one position for all beams), then the walk of the
+    back-pointers: LongTensor [B, n_new] (CPU).  ``tag``: what the step's launches depend on besides the beam search's scalars."""
+    step = device_step
+    if model.decode_graphs and model.device.type == "cuda":
+        # hipGraph replay of device_step (~430 launches: ps_slm_amd/graphs.py), keyed by the scalars baked into its kernel arguments
+        key = (tag, bs.B, bs.S, bs.nb, bs.S + bs.max_new, bs.max_new, bs.eos, bs.min_length)
+        step = lambda: model._dec_graphs.run(key, device_step, lambda: model._buf_gen)
+    if model.device.type == "cuda":
+        # the host issues positions ahead of the device and looks at the pinned "done" word DONE_POLL_DEPTH positions late
+        # (an event per position); positions issued after the device finished are no-ops for the beam state
+        inflight = collections.deque()
+        for _ in range(bs.max_new - 1):
+            step()
+            ev = torch.cuda.Event()
+            ev.record()
+            inflight.append(ev)
+            if len(inflight) > DONE_POLL_DEPTH:
+                inflight.popleft().synchronize()
+                if int(bs.done_host[0]):
+                    break
+        torch.cuda.synchronize()
+    else:
+        while not int(bs.ctl[1]):
+            step()
+    return bs.result(pad)
+
+
 def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
                          eos_token_id=None, pad_token_id=None):
     """st: a prepared state whose projector output (st.dev['y2']) is ready.  Returns LongTensor [B, n_new] (CPU)."""
@@ -168,35 +231,17 @@ def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, 
             return beam_search_generate(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos_token_id, pad_token_id)
         finally:
             model.llm, model._lora_run = keep
-    ops, geo, llm = model.ops, model.geo, model.llm
-    B, S, nb = st.B, st.S, num_beams
-    min_length = effective_min_length(min_length, S)
-    # limits of the device beam search (tasu_beam_update, tasu_decode_step_prologue: include/tasu_hip.h), checked BEFORE the prefill
-    if not 1 <= nb <= BEAM_MAX_NB:
-        raise ValueError(f"num_beams={nb}: the device beam search serves 1..{BEAM_MAX_NB} beams")
-    if B > BEAM_MAX_B:
-        raise ValueError(f"{B} utterances per generate() call: the device beam search serves at most {BEAM_MAX_B}")
-    if S + max_new_tokens > DECODE_MAX_CTX:
-        raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds the cache attention's context limit {DECODE_MAX_CTX}")
-    if max_new_tokens < 1:
-        raise ValueError("max_new_tokens must be >= 1")
-    M, K = B * nb, 2 * nb
-    D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
-    Vp, LDQ, W = rup(V, 64), (H + 2 * G) * HD, G * HD
-    eos = geo.eos_id if eos_token_id is None else eos_token_id
-    pad = eos if pad_token_id is None else pad_token_id
-    ctx = S + max_new_tokens
-    scale = HD ** -0.5
-    bf, f32, i32 = torch.bfloat16, torch.float32, torch.int32
-    buf = model._buf
+    ops, geo = model.ops, model.geo
+    min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, DECODE_MAX_CTX,
+                                         "the cache attention's")
     # ---- prefill with the training-forward kernels (no loss)
     model.forward_llm(st, compute_loss=False, need_backward=False, logits_rows="none")
     # decode-step weights in the order the streaming kernels consume them (built once per model), and the decision whether the
     # step's bf16 activations travel between its kernels in that order too (ops.begin_decode)
-    llm.prepare_decode(ops)
-    ops.begin_decode(D, H * HD, I)
+    model.llm.prepare_decode(ops)
+    ops.begin_decode(geo.llm_dim, geo.llm_heads * HD, geo.llm_inter)
     try:
-        return _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_penalty, eos, pad)
+        return _decode_after_prefill(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos, pad)
     finally:
         ops.end_decode()
 
@@ -255,25 +300,18 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
     Vp, LDQ, W = rup(V, 64), (H + 2 * G) * HD, G * HD
     ctx = S + max_new_tokens
-    scale = HD ** -0.5
     bf, f32, i32 = torch.bfloat16, torch.float32, torch.int32
     buf = model._buf
     d = st.dev
-    # KV cache [L][M, ctx, W] + the beam row index (include/tasu_hip.h): the prompt is stored once per utterance and a
-    # beam reorder permutes 4-byte index entries once per step instead of copying K/V in every layer
+    # KV cache [L][M, ctx, W] + the beam row index
     kc = buf("dec_kc", (L, M * ctx * W), bf)
     vc = buf("dec_vc", (L, M * ctx * W), bf)
-    index = buf("dec_index", (M, ctx), i32)
-    index_tmp = buf("dec_index_tmp", (M, ctx), i32)
-    ops.kv_index_init(index, B, nb, S, ctx)
-    ops.kv_index_init(index_tmp, B, nb, S, ctx)
+    index, index_tmp = kv_row_index(model, B, nb, S, ctx)
     for l in range(L):
         ops.kv_fill(d["qkv"][l], kc[l], vc[l], B, S, H, G, nb, ctx)
     valid = st.plan.key_mask[:, :S].sum(1).astype(np.int64)               # real tokens per prompt
-    kstart_h = np.repeat(S - valid, nb).astype(np.int32)                   # left padding is at the front
-    kstart = model._upload("dec_kstart", kstart_h)
+    kstart, last_rows = prompt_rows(model, B, S, nb, valid)
     # logits of the last prompt position of every batch row
-    last_rows = model._upload("dec_last_rows", (np.arange(B, dtype=np.int32) + 1) * S - 1)
     xl = buf("dec_xlast", (B, D), f32)
     ops.embed_rows(d["xs"][2 * L], last_rows, xl, B, D)                    # row gather out of the residual stream
     xn = buf("dec_xn", (Mp, D), bf)
@@ -283,7 +321,6 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     tv = buf("dec_topv", (M, K), f32)
     ti = buf("dec_topi", (M, K), i32)
     bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid)
-    model._last_beam = bs                                                  # (tests read the final scores / back-pointers)
     ops.logprob_topk(logits, B, V, K, bs.banned, 1, tv, ti)
     ops.beam_update(tv, ti, bs, True)                                      # first position: only beam 0 exists
     x = buf("dec_x", (M, D), f32)
@@ -300,79 +337,19 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     # The weight-streaming kernels take at most 64 rows: more beams than that (B > 16 at 4 beams) run them in row chunks
     # (the weights are then streamed once per chunk; K/V, attention and top-k are not chunked).
     chunks = [(m0, min(64, M - m0)) for m0 in range(0, M, 64)]
-    kcv, vcv = kc.view(L, M, ctx * W), vc.view(L, M, ctx * W)
     def device_step():
         """One generated position for all M beams: beam reorder of the row index (parents of the previous step), then the
         28-layer single-token pass over the cache, lm_head, the per-row top-k and the beam update."""
         ops.decode_step_prologue(llm.embed, ids_d, x, llm.layers[0]["ln1"], xn, geo.rms_eps, pos_d, cos, sin, HD, geo.rope_theta, index,
                                  index_tmp, src_d, slot_d, nb, M, D, ctx)
-        per_gemm_layers()
+        layers_per_gemm(ops, geo, llm.layers, llm.norm, x, x2, xn, qkv, ao, act, cos, sin, kc, vc, index, kstart, slot_d, lens_d,
+                        M, ctx, ws, normed=True)
         for m0, mc in chunks:
             ops.gemm_skinny(xn[m0:m0 + mc], llm.head, logits[m0:m0 + mc], mc, V, D, ws)
         ops.logprob_topk(logits, M, V, K, bs.banned, 1, tv, ti)
         ops.beam_update(tv, ti, bs, False)
 
-    def per_gemm_layers():
-        layers_per_gemm(ops, geo, llm.layers, llm.norm, x, x2, xn, qkv, ao, act, cos, sin, kc, vc, index, kstart, slot_d, lens_d,
-                        M, ctx, ws, normed=True)
-
-    # hipGraph replay of device_step (~430 launches): the first step of a shape runs eagerly, the second is captured.
-    # A graph is only valid for the buffers it was captured on (grow-only workspace: same generation = same addresses) and
-    # for the scalars baked into its kernel arguments; a small LRU bounds the cache (real data gives almost every batch its
-    # own prompt length).
-    use_graphs = model.decode_graphs and model.device.type == "cuda"
-    graphs, seen_cnt = model._dec_graphs, model._dec_seen
     # the launch / layout switches decide which kernels device_step issues: a graph captured under one setting must not be
     # replayed under another (in-process A/B runs)
     switches = tuple(bool(getattr(ops, n, False)) for n in ("use_stream", "dec_frag", "dec_frag_act", "dec_down_slabs", "dec_prologue"))
-    key = ("decode", B, S, nb, ctx, max_new_tokens, int(eos), int(min_length), switches, model._buf_gen)
-
-    def run_step():
-        if not use_graphs:
-            return device_step()
-        for old in [k for k in graphs if k[-1] != model._buf_gen]:
-            del graphs[old]                                      # captured on addresses that have since been freed
-            seen_cnt.pop(old, None)
-        g = graphs.get(key)
-        if g is not None:
-            graphs.move_to_end(key)
-            return g.replay()
-        seen = seen_cnt.get(key, 0)
-        seen_cnt[key] = seen + 1
-        if seen < 1:
-            return device_step()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        import gc
-        gc_was = gc.isenabled()
-        gc.disable()                                             # (no cyclic collection inside a capture: TasuModel._graphed)
-        try:
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                device_step()
-        finally:
-            if gc_was:
-                gc.enable()
-        graphs[key] = g
-        while len(graphs) > DECODE_GRAPH_CACHE:
-            old, _ = graphs.popitem(last=False)
-            seen_cnt.pop(old, None)
-        g.replay()
-
-    if model.device.type == "cuda":
-        # the host issues positions ahead of the device and looks at the pinned "done" word DONE_POLL_DEPTH positions late
-        # (an event per position); positions issued after the device finished are no-ops for the beam state
-        inflight = collections.deque()
-        for _ in range(max_new_tokens - 1):
-            run_step()
-            ev = torch.cuda.Event()
-            ev.record()
-            inflight.append(ev)
-            if len(inflight) > DONE_POLL_DEPTH:
-                inflight.popleft().synchronize()
-                if int(bs.done_host[0]):
-                    break
-        torch.cuda.synchronize()
-    else:
-        while not int(bs.ctl[1]):
-            run_step()
-    return bs.result(pad)
+    return decode_positions(model, bs, device_step, pad, ("decode", switches))

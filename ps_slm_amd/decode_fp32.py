@@ -16,12 +16,10 @@ the 17 rounding-stable ones and the text + audio fixture (tests/test_gpu_model.p
 
 HBM-bound like the bf16 step, on twice the bytes: 6.2 GB of fp32 weights per generated position at Qwen2.5-1.5B.
 """
-import collections
-
 import numpy as np
 import torch
 
-from .decode import BEAM_MAX_B, BEAM_MAX_NB, DECODE_GRAPH_CACHE, DONE_POLL_DEPTH, DeviceBeam, effective_min_length
+from .decode import DeviceBeam, decode_positions, generate_args, kv_row_index, prompt_rows
 from .model import HD, StepState, rup
 
 F32_MAX_CTX = 2048          # tasu_f32_attn_*: keys per query row
@@ -180,7 +178,7 @@ def forward_fp32(model, st: StepState, compute_loss=True):
     Multitask/utils/deepspeed_utils.py:394-498 and any ``model(**batch)`` outside autocast): fp32 logits for every position
     (``st.dev['logits']`` [B * S, V]), the shifted CE over the labelled rows and the token accuracy (``st.dev['loss_out']`` =
     [mean loss, accuracy, count, 1 / count]).  No activations are kept: there is no fp32 backward."""
-    ops, geo, llm = model.ops, model.geo, model.llm
+    ops, geo = model.ops, model.geo
     xn0, _, _, _ = prompt_pass_fp32(model, st)
     M0, D, V = st.B * st.S, geo.llm_dim, geo.llm_vocab
     f32, i32 = torch.float32, torch.int32
@@ -204,25 +202,16 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     """st: a prepared state (prepare_text / prepare_audio).  Returns LongTensor [B, n_new] (CPU)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
+    min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, F32_MAX_CTX,
+                                         "the fp32 attention's")
     B, S, nb = st.B, st.S, num_beams
-    min_length = effective_min_length(min_length, S)
-    if not 1 <= nb <= BEAM_MAX_NB:
-        raise ValueError(f"num_beams={nb}: the device beam search serves 1..{BEAM_MAX_NB} beams")
-    if B > BEAM_MAX_B:
-        raise ValueError(f"{B} utterances per generate() call: the device beam search serves at most {BEAM_MAX_B}")
-    if max_new_tokens < 1:
-        raise ValueError("max_new_tokens must be >= 1")
     ctx = S + max_new_tokens
-    if ctx > F32_MAX_CTX:
-        raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds the fp32 attention's context limit {F32_MAX_CTX}")
-    M0, M, K = B * S, B * nb, 2 * nb
+    M, K = B * nb, 2 * nb
     D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
     LDQ, W = (H + 2 * G) * HD, G * HD
-    eos = geo.eos_id if eos_token_id is None else eos_token_id
-    pad = eos if pad_token_id is None else pad_token_id
     scale = HD ** -0.5
     f32, i32 = torch.float32, torch.int32
-    buf, d = model._buf, st.dev
+    buf = model._buf
     ws = _gemm_ws(model)
     frag = _fragments(model)
     head = weights_f32(model)["head"] if frag is None else ops.f32_weight(frag["head"], M, ws)
@@ -230,23 +219,18 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     # ---- KV cache (fp32) + the beam row index of the bf16 path
     kc = buf("f32_kc", (L, M * ctx * W), f32)
     vc = buf("f32_vc", (L, M * ctx * W), f32)
-    index = buf("dec_index", (M, ctx), i32)
-    index_tmp = buf("dec_index_tmp", (M, ctx), i32)
-    ops.kv_index_init(index, B, nb, S, ctx)
-    ops.kv_index_init(index_tmp, B, nb, S, ctx)
+    index, index_tmp = kv_row_index(model, B, nb, S, ctx)
     # ---- prompt pass; every layer's rotated K / V go to the cache row of the utterance's first beam
     xn0, _, valid, left = prompt_pass_fp32(model, st, on_layer=lambda l, qkv_l: ops.f32_kv_fill(qkv_l, kc[l], vc[l], B, S, H, G, nb, ctx))
     if not left:
         raise ValueError("fp32 decode expects left-padded prompts (what the reference's inference collator builds)")
-    kstart = model._upload("dec_kstart", np.repeat(S - valid, nb).astype(np.int32), flush=False)
-    last_rows = model._upload("dec_last_rows", (np.arange(B, dtype=np.int32) + 1) * S - 1)
+    kstart, last_rows = prompt_rows(model, B, S, nb, valid)
     x, xn = buf("f32_x", (M, D), f32), buf("f32_xn", (M, D), f32)
     logits = buf("f32_logits", (M, V), f32)
     ops.embed_rows(xn0, last_rows, xn, B, D)                    # the final-normed last prompt position of every utterance
     ops.f32_gemm(xn, weights_f32(model)["head"], logits, B, V, D, ws=ws)
     tv, ti = buf("dec_topv", (M, K), f32), buf("dec_topi", (M, K), i32)
     bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid)
-    model._last_beam = bs
     topk_ws = buf("f32_topk_ws", (M * 16 * (2 + 2 * K),), f32)               # the row split over 16 workgroups (tasu_f32_logprob_topk)
     ops.f32_logprob_topk(logits, B, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
     ops.beam_update(tv, ti, bs, True)
@@ -271,50 +255,4 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
         ops.f32_logprob_topk(logits, M, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
         ops.beam_update(tv, ti, bs, False)
 
-    use_graphs = model.decode_graphs and model.device.type == "cuda"
-    graphs, seen_cnt = model._dec_graphs, model._dec_seen
-    key = ("decode_fp32", B, S, nb, ctx, max_new_tokens, int(eos), int(min_length), model._buf_gen)
-
-    def run_step():
-        if not use_graphs:
-            return device_step()
-        for old in [k for k in graphs if k[-1] != model._buf_gen]:
-            del graphs[old]
-            seen_cnt.pop(old, None)
-        g = graphs.get(key)
-        if g is not None:
-            graphs.move_to_end(key)
-            return g.replay()
-        seen = seen_cnt.get(key, 0)
-        seen_cnt[key] = seen + 1
-        if seen < 1:
-            return device_step()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        import gc
-        gc_was = gc.isenabled()
-        gc.disable()                                             # (no cyclic collection inside a capture: TasuModel._graphed)
-        try:
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                device_step()
-        finally:
-            if gc_was:
-                gc.enable()
-        graphs[key] = g
-        while len(graphs) > DECODE_GRAPH_CACHE:
-            old, _ = graphs.popitem(last=False)
-            seen_cnt.pop(old, None)
-        g.replay()
-
-    inflight = collections.deque()
-    for _ in range(max_new_tokens - 1):
-        run_step()
-        ev = torch.cuda.Event()
-        ev.record()
-        inflight.append(ev)
-        if len(inflight) > DONE_POLL_DEPTH:
-            inflight.popleft().synchronize()
-            if int(bs.done_host[0]):
-                break
-    torch.cuda.synchronize()
-    return bs.result(pad)
+    return decode_positions(model, bs, device_step, pad, "decode_fp32")

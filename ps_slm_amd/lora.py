@@ -326,7 +326,6 @@ def merged_llm(model):
             model.ops.forget_decode_weights([w[k].data_ptr() for w in m.layers for k in ("wqkv", "wo", "wgu", "wd")])
         m._decode_ready = False
         model._dec_graphs.clear()
-        model._dec_seen.clear()
     lp._merged, lp._merged_version = m, lp.version
     return m
 
@@ -359,7 +358,6 @@ def merged_llm_f32(model):
         if fr is not None:
             m["frag_head"] = fr["head"]
         model._dec_graphs.clear()
-        model._dec_seen.clear()
     tg = lp.cfg.target_modules
     a_op = torch.zeros(max(lp.dims[t][1] for t in tg), rk, dtype=f32, device=p.device)     # s B of one target, rank columns padded
     b_op = torch.zeros(max(lp.dims[t][0] for t in tg), rk, dtype=f32, device=p.device)     # A^T of one target

@@ -21,7 +21,6 @@ HBM layout (sized for 288 GB: everything stays resident, nothing is recomputed):
     dimension is padded to a multiple of 64 with zeros (pad columns provably stay zero under AdamW).
   * per layer saved for backward: x_in, x_mid (fp32), rstd1/2, rotated qkv, attention out, lse, gate|up.
 """
-import collections
 import math
 import os
 from dataclasses import dataclass, field
@@ -29,6 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from .graphs import GraphCache
 from .merge import build_merge_plan
 from .ops import GEMM_BF16, GEMM_F32, GEMM_RESID, LN_BWD_SPLIT
 
@@ -461,12 +461,11 @@ class TasuModel:
         # of a position without a label feeds nothing after that layer's attention (its K / V, which all rows still produce) --
         # like the loss head (_loss_on_labelled_rows).  Same loss and gradients (tests compare both settings of the attribute).
         self.tail_rows = True
-        self.graph_cache_size = 64
         self.decode_graphs = True      # the decode step (ps_slm_amd/decode.py) is always replayed as a graph on the GPU
-        self._graphs = {}
-        self._graph_seen = {}
         self._buf_gen = 0              # bumped whenever a named workspace buffer is re-allocated (grown)
-        self._dec_graphs, self._dec_seen = collections.OrderedDict(), {}   # decode-step graphs (ps_slm_amd/decode.py): small LRU
+        self._graphs = GraphCache(64)
+        # decode-step graphs (ps_slm_amd/decode.py): a small LRU, almost every real batch has its own prompt length
+        self._dec_graphs = GraphCache(8)
         self._done_host = None         # pinned "decode finished" word the beam-update kernel writes
         self.lora = None               # ps_slm_amd.lora.LoraParams once enable_lora() ran (use_peft=true)
         self.freeze_projector = False  # train_config.freeze_projector (ps-slm.py:50-54): the projector's weight gradients, exchange and
@@ -501,9 +500,7 @@ class TasuModel:
         if self._enc_ahead is not None:
             self._enc_ahead["ready"].synchronize()
             self._enc_ahead = None
-        for k in [k for k in self._graphs if k[:2] == ("region", "encoder")]:
-            del self._graphs[k]
-            self._graph_seen.pop(k, None)
+        self._graphs.drop(lambda k: k[:2] == ("region", "encoder"))
 
     def init_random(self, seed=1234, with_encoder=False):
         self.llm.init_random(seed)
@@ -576,7 +573,7 @@ class TasuModel:
         self.lora.init_default(seed)
         self.lora.seed_dropout(seed)
         self._lora_run = LoraRunner(self)
-        self._graphs, self._graph_seen = {}, {}
+        self._graphs.clear()
         self.sync_projector_copies()
 
     def lora_spans(self, n=7):
@@ -1213,61 +1210,12 @@ class TasuModel:
         self._flush_uploads()                           # (no-op unless a caller deferred an upload and forgot it)
         if not (self.use_graphs and self.device.type == "cuda"):
             return fn()
-        g = self._graphs.get(key)
-        if g is not None and g[2] != self._buf_gen:
-            # a workspace buffer has grown since the capture (a larger batch shape came by): the graph holds freed
-            # addresses.  Drop every graph of that generation and start over for this key.
-            self._graphs = {k: v for k, v in self._graphs.items() if v[2] == self._buf_gen}
-            self._graph_seen.pop(key, None)
-            g = None
-        if g is not None:
-            self._graphs[key] = self._graphs.pop(key)     # most recently used
-            g[0].replay()
-            for k, v in g[1].items():                 # the views the captured code published into st.dev
-                st.dev.setdefault(k, v)
-            return
-        seen = self._graph_seen.get(key, 0)
-        self._graph_seen[key] = seen + 1
-        if seen < 1:
-            return fn()                              # eager warm-up: buffer allocation, lazy kernel attributes
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        before = set(st.dev)
-        gen = self._buf_gen
-        # The cyclic garbage collector must not run inside a capture: an unreachable CUDAGraph of an earlier model (a cycle freed
-        # at a moment of the collector's choosing) would be destroyed while this stream is capturing -- hipGraphDestroy then fails
-        # with "operation not permitted when stream is capturing" inside a destructor and takes the process down (seen in bench.py
-        # between two legs).  torch.cuda.graph collects once before the capture begins; nothing may be collected until it ends.
-        import gc
-        gc_was = gc.isenabled()
-        gc.disable()
-        try:
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):   # other threads (RCCL watchdog) may call into HIP
-                try:
-                    fn()
-                except BaseException:
-                    # an exception that unwinds out of a capture takes the process down in ~CUDAGraph: say what it was first
-                    import traceback
-                    traceback.print_exc()
-                    raise
-        finally:
-            if gc_was:
-                gc.enable()
-        if gen != self._buf_gen:                      # a buffer grew DURING the capture: do not keep the graph
-            return
-        self._graphs[key] = (graph, {k: v for k, v in st.dev.items() if k not in before}, gen)
-        while len(self._graphs) > self.graph_cache_size:          # LRU: dicts keep insertion order, replays re-insert
-            old = next(iter(self._graphs))
-            del self._graphs[old]
-            self._graph_seen.pop(old, None)
-        graph.replay()
+        self._graphs.run(key, fn, lambda: self._buf_gen, None if st is None else st.dev)
 
     def graphed_region(self, key, fn):
         """Runs ``fn`` (a launch sequence that depends only on ``key`` and on the contents of persistent workspace
         buffers) eagerly or, with graphs enabled, as a captured hipGraph keyed by ``key`` (+ the workspace generation)."""
-        class _NoState:
-            dev = {}
-        self._graphed(("region",) + tuple(key), fn, _NoState())
+        self._graphed(("region",) + tuple(key), fn, None)
 
     def _shape_key(self, st, tag):
         return (tag, st.path, st.B, st.S, st.Ra, st.Rap, st.Fap, st.nLp, self.keep_logits, self.lora is not None and self.training)

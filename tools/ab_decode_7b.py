@@ -22,7 +22,7 @@ NEW = 96
 def run(stream, new, prenorm=True):
     core.ops.dec_stream_7b = stream
     core.ops.dec_prenorm = prenorm
-    core._dec_graphs.clear(); core._dec_seen.clear()
+    core._dec_graphs.clear()
     st = core.prepare_text(ids, am, None, raw["post_ids"], None, None)
     core.forward_projector_text(st)
     return beam_search_generate(core, st, num_beams=4, max_new_tokens=new, eos_token_id=-1, pad_token_id=0)

@@ -19,7 +19,7 @@ am = torch.ones_like(ids, dtype=torch.bool)
 
 def run(order):
     core.ops.dec_split_order = order
-    core._dec_graphs.clear(); core._dec_seen.clear()
+    core._dec_graphs.clear()
     st = core.prepare_text(ids, am, None, raw["post_ids"], None, None)
     core.forward_projector_text(st)
     return beam_search_generate(core, st, num_beams=4, max_new_tokens=200, eos_token_id=-1, pad_token_id=0)

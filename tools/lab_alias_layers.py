@@ -47,6 +47,6 @@ res = {"real": [], "layers_aliased": []}
 for rnd in range(3):
     for name in ("real", "layers_aliased"):
         core.llm.layers[:] = real_layers if name == "real" else [real_layers[0]] * len(real_layers)
-        core._graphs.clear(); core._graph_seen.clear()
+        core._graphs.clear()
         res[name].append(round(timed(), 3))
 print(json.dumps({"ms_per_step": res}))

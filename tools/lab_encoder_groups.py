@@ -4,6 +4,7 @@ import os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ps_slm_amd.encoder import EncoderWeights, encoder_posterior
+from ps_slm_amd.graphs import GraphCache
 from ps_slm_amd.model import Geometry, TasuModel
 from ps_slm_amd.ops import HipOps
 from ps_slm_amd.synthetic import synthetic_text_batch
@@ -21,7 +22,7 @@ class View:                                  # the slice of TasuModel the encode
 def view():
     m = TasuModel.__new__(TasuModel)
     m.geo, m.ops, m.device, m.encoder = geo, HipOps(), torch.device("cuda"), enc
-    m._ws, m._buf_gen, m._graphs, m._graph_seen, m.use_graphs, m.graph_cache_size = {}, 0, {}, {}, True, 64
+    m._ws, m._buf_gen, m._graphs, m.use_graphs = {}, 0, GraphCache(64), True
     return m
 
 res = {}

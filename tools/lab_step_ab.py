@@ -46,6 +46,6 @@ res = {v[0]: [] for v in variants}
 for rnd in range(3):
     for name, f, b in variants:
         core.ops.attn_kernel = {"fwd": f, "bwd": b}
-        core._graphs.clear(); core._graph_seen.clear()
+        core._graphs.clear()
         res[name].append(round(timed(), 3))
 print(json.dumps({"ms_per_step": res}))

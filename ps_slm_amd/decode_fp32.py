@@ -6,7 +6,9 @@ so its tokens are those of an fp32 forward pass.  The bf16 path (ps_slm_amd/deco
 matter; this path computes what the reference computes: the fp32 projector on the master weights (project_fp32: linear-silu,
 linear, cov1d-linear, and cross-attention through the fused tasu_f32_ca_attn over the input embedding table), fp32 embeddings and
 residual stream, fp32 q|k|v / RoPE / attention / MLP on fp32 copies of the frozen Qwen2 weights (with use_peft: the merged
-W + s B A of ps_slm_amd.lora.merged_llm_f32, one accessor, weights_f32), an fp32 KV cache, fp32 logits, log-softmax and top-k -- csrc/fp32.hip through the C-ABI (``tasu_f32_*``).  The beam search itself is the
+W + s B A of ps_slm_amd.lora.merged_llm_f32, one accessor, weights_f32), an fp32 KV cache, fp32 logits, log-softmax and top-k -- csrc/fp32.hip through the C-ABI (``tasu_f32_*``).  prompt_pass_fp32
+is the only fp32 decoder forward: the eval forward, generate()'s prefill and, with its activations kept, the fp32 training step
+(ps_slm_amd/train_fp32.py) run it.  The beam search itself is the
 same device-side bookkeeping as the bf16 path's (``tasu_beam_update``, the cache row index, ``DeviceBeam``), and a generated
 position is one hipGraph replay.  Nothing is rounded to bf16; sums run in another order than the reference's CPU BLAS (fp32 MFMA,
 K ascending, K-range slabs added in ascending order: deterministic).  The audio branch runs the frozen SenseVoice encoder, the CTC
@@ -57,13 +59,14 @@ def _fragments(model):
     return fr
 
 
-def project_fp32(model, st: StepState):
+def project_fp32(model, st: StepState, keep=None):
     """The projector in fp32 on the master weights (``pr.view(pr.p, ...)``, the layout of the bf16 images): st.dev['y2_f32'] [Rap, D].
     linear-silu (EncoderProjectorLinearSiLU, Multitask/model/projector.py:128-151): LayerNorm -> Linear -> SiLU -> Linear;
     linear (EncoderProjectorConcat, :28-49): k consecutive frames as one row -> Linear -> ReLU -> Linear;
     cov1d-linear (EncoderProjectorCov1d, :53-73): Conv1d(kernel = stride = k) as one GEMM over the k-frame rows -> ReLU -> Linear ->
     ReLU -> Linear;  cross-attention (EncoderProjectorCTCCA, :104-126): Q = W_q(post), then tasu_f32_ca_attn over the fp32 input
-    embedding table."""
+    embedding table.  ``keep`` (the training step, linear-silu only): the LayerNorm statistics are written and the SiLU runs on its
+    own after W1, so that the backward can read xn_p, mean, rstd, h_pre and h from it."""
     ops, pr = model.ops, model.proj
     f32 = torch.float32
     Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
@@ -83,7 +86,8 @@ def project_fp32(model, st: StepState):
         return y2
     if pr.has_norm:
         x = model._buf("f32_proj_xn", (Fap, Kp), f32)
-        ops.layernorm_fwd(st.dev["post"], pr.view(pr.p, "norm.weight"), pr.view(pr.p, "norm.bias"), x, None, None, Fap, K, model.geo.ln_eps)
+        mean, rstd = (None, None) if keep is None else (model._buf("ln_mean", (Fap,), f32), model._buf("ln_rstd", (Fap,), f32))
+        ops.layernorm_fwd(st.dev["post"], pr.view(pr.p, "norm.weight"), pr.view(pr.p, "norm.bias"), x, mean, rstd, Fap, K, model.geo.ln_eps)
     else:
         x = st.dev["post"]                                     # linear / cov1d-linear: the posterior as it is
     x = x.view(Rap, pr.k * Kp)                                 # k consecutive frames = one projector row (k = 1: linear-silu)
@@ -92,7 +96,13 @@ def project_fp32(model, st: StepState):
         ops.f32_gemm(x, pr.view(pr.p, "conv1d.weight"), c0, Rap, Kp, pr.k * Kp, bias=pr.view(pr.p, "conv1d.bias"), act=2, ws=ws)
         x = c0
     h = model._buf("f32_proj_h", (Rap, Hb), f32)
-    ops.f32_gemm(x, pr.view(pr.p, pr.n_w1), h, Rap, Hb, pr.kin * Kp, bias=pr.view(pr.p, pr.n_b1), act=1 if pr.has_norm else 2, ws=ws)
+    if keep is None:
+        ops.f32_gemm(x, pr.view(pr.p, pr.n_w1), h, Rap, Hb, pr.kin * Kp, bias=pr.view(pr.p, pr.n_b1), act=1 if pr.has_norm else 2, ws=ws)
+    else:
+        h_pre = model._buf("f32t_h_pre", (Rap, Hb), f32)
+        ops.f32_gemm(x, pr.view(pr.p, pr.n_w1), h_pre, Rap, Hb, pr.kin * Kp, bias=pr.view(pr.p, pr.n_b1), ws=ws)
+        ops.f32_silu(h_pre, h)
+        keep.update(xn_p=x, mean=mean, rstd=rstd, h_pre=h_pre, h=h)
     ops.f32_gemm(h, pr.view(pr.p, pr.n_w2), y2, Rap, Do, Hb, bias=pr.view(pr.p, pr.n_b2), ws=ws)
     st.dev["y2_f32"] = y2
     return y2
@@ -107,10 +117,13 @@ def weights_f32(model):
     return model.llm.f32
 
 
-def _layer_fp32(model, l, x, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, cache=None, ctx=0, frag=None):
-    """One decoder layer; in: xn = RMSNorm(x, ln1[l]); out: x updated, xn = the NEXT norm of it (ln1[l + 1], or the final norm).
+def _layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, cache=None, ctx=0, frag=None,
+                keep_gu=False):
+    """One decoder layer; in: xn = RMSNorm(x_in, ln1[l]); out: x_mid = x_in + attention, x_out = x_mid + MLP, xn = the NEXT norm of
+    x_out (ln1[l + 1], or the final norm).  Decode and eval pass one buffer three times; the training step passes its kept slices.
     Every projection carries the row-wise kernel behind it in the launch that sums its K-range slabs (tasu_f32_gemm_qkv_rope,
-    _resid_rmsnorm, _swiglu): 9 launches per layer at <= 64 beam rows instead of 13."""
+    _resid_rmsnorm, _swiglu): 9 launches per layer at <= 64 beam rows instead of 13.  ``keep_gu``: gate|up is kept in ``gu`` for
+    the backward, so it runs as its own GEMM and SwiGLU instead of the fused finisher."""
     ops, geo, llm = model.ops, model.geo, model.llm
     D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
     f, w = weights_f32(model)["layers"][l], llm.layers[l]
@@ -118,10 +131,14 @@ def _layer_fp32(model, l, x, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, w
     kc_l, vc_l, slot = cache if cache is not None else (None, None, None)
     ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, cos_t, sin_t, rows, H, G, D, ws, kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
     attend(l, qkv, ao)
-    ops.f32_gemm_resid_rmsnorm(ao, f["wo"], x, w["ln2"], xn, rows, D, H * HD, geo.rms_eps, ws, resid=x)
+    ops.f32_gemm_resid_rmsnorm(ao, f["wo"], x_mid, w["ln2"], xn, rows, D, H * HD, geo.rms_eps, ws, resid=x_in)
     wgu, wd = (f["wgu"], f["wd"]) if frag is None else (ops.f32_weight(frag["layers"][l]["wgu"], rows, ws), ops.f32_weight(frag["layers"][l]["wd"], rows, ws))
-    ops.f32_gemm_swiglu(xn, wgu, gu, act, rows, I, D, ws)
-    ops.f32_gemm_resid_rmsnorm(act, wd, x, next_norm, xn, rows, D, I, geo.rms_eps, ws, resid=x)
+    if keep_gu:
+        ops.f32_gemm(xn, wgu, gu, rows, 2 * I, D, ws=ws)
+        ops.f32_swiglu(gu, act, rows, I)
+    else:
+        ops.f32_gemm_swiglu(xn, wgu, gu, act, rows, I, D, ws)
+    ops.f32_gemm_resid_rmsnorm(act, wd, x_out, next_norm, xn, rows, D, I, geo.rms_eps, ws, resid=x_mid)
 
 
 def _need_f32(model):
@@ -130,11 +147,14 @@ def _need_f32(model):
                            "(model_factory sets LLMWeights.keep_f32 before loading)")
 
 
-def prompt_pass_fp32(model, st: StepState, on_layer=None):
-    """The decoder over the merged prompt in fp32: projector -> embedding merge -> 28 layers (causal attention; a batch's padding is
-    on one side: left-padded prompts mask their first ``S - valid`` keys, right-padded training batches need no key mask under the
-    causal one -- their padded QUERY rows hold garbage nobody reads).  ``on_layer(l, qkv)``: called with the layer's rotated q|k|v
-    (generate() fills its cache there).  Returns (xn0 = the final-normed hidden states [B * S, D], x0 = the residual stream)."""
+def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
+    """The decoder over the merged prompt in fp32, the one fp32 decoder forward of the eval forward, generate()'s prefill and the
+    training step: projector -> embedding merge -> 28 layers (causal attention; a batch's padding is on one side: left-padded
+    prompts mask their first ``S - valid`` keys, right-padded training batches need no key mask under the causal one -- their padded
+    QUERY rows hold garbage nobody reads).  ``on_layer(l, qkv)``: called with the layer's rotated q|k|v (generate() fills its cache
+    there).  ``keep`` (a dict: the training step): every layer's activations go to stacked buffers -- layer l reads xs[2l] and
+    writes xs[2l + 1] and xs[2l + 2] -- gate|up runs unfused, and ``keep`` receives what backward_fp32 reads (xs, qkvs, aos, gus,
+    cos, sin, kstart and the projector's, project_fp32).  Returns (xn0 = the final-normed hidden states [B * S, D], valid, left)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     B, S = st.B, st.S
@@ -153,24 +173,32 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None):
     f32 = torch.float32
     buf, d = model._buf, st.dev
     ws = _gemm_ws(model)
-    y2 = project_fp32(model, st)
+    y2 = project_fp32(model, st, keep)
     kstart_b = model._upload("f32_kstart_b", ((S - valid) if left else np.zeros(B, dtype=np.int64)).astype(np.int32))
-    x0 = buf("f32_x0", (M0, D), f32)
-    ops.f32_embed_merge(llm.embed, y2, d["kind"], d["idx"], x0, M0, D)
+    if keep is None:                       # one buffer per activation, rewritten by every layer
+        x0 = buf("f32_x0", (M0, D), f32)
+        xs, qkvs = [x0] * (2 * L + 1), [buf("f32_qkv0", (M0, LDQ), f32)] * L
+        aos, gus = [buf("f32_ao0", (M0, H * HD), f32)] * L, [buf("f32_gu0", (M0, 2 * I), f32)] * L
+    else:
+        xs, qkvs = buf("f32t_xs", (2 * L + 1, M0, D), f32), buf("f32t_qkv", (L, M0, LDQ), f32)
+        aos, gus = buf("f32t_ao", (L, M0, H * HD), f32), buf("f32t_gu", (L, M0, 2 * I), f32)
+    ops.f32_embed_merge(llm.embed, y2, d["kind"], d["idx"], xs[0], M0, D)
     cos0, sin0 = buf("f32_cos0", (M0, HD // 2), f32), buf("f32_sin0", (M0, HD // 2), f32)
     ops.rope_table(d["pos"], cos0, sin0, HD, geo.rope_theta)
-    xn0, qkv0, ao0 = buf("f32_xn0", (M0, D), f32), buf("f32_qkv0", (M0, LDQ), f32), buf("f32_ao0", (M0, H * HD), f32)
-    gu0, act0 = buf("f32_gu0", (M0, 2 * I), f32), buf("f32_act0", (M0, I), f32)
+    xn0, act0 = buf("f32_xn0", (M0, D), f32), buf("f32_act0", (M0, I), f32)
 
     def attend_prompt(l, qkv, ao):
         if on_layer is not None:
             on_layer(l, qkv)
         ops.f32_attn_prefill(qkv, kstart_b, ao, B, S, H, G, scale)
 
-    ops.f32_rmsnorm(x0, llm.layers[0]["ln1"], xn0, M0, D, geo.rms_eps)
+    ops.f32_rmsnorm(xs[0], llm.layers[0]["ln1"], xn0, M0, D, geo.rms_eps)
     for l in range(L):
-        _layer_fp32(model, l, x0, xn0, qkv0, ao0, gu0, act0, M0, cos0, sin0, attend_prompt, ws)
-    return xn0, x0, valid, left
+        _layer_fp32(model, l, xs[2 * l], xs[2 * l + 1], xs[2 * l + 2], xn0, qkvs[l], aos[l], gus[l], act0, M0, cos0, sin0, attend_prompt,
+                    ws, keep_gu=keep is not None)
+    if keep is not None:
+        keep.update(xs=xs, qkvs=qkvs, aos=aos, gus=gus, cos=cos0, sin=sin0, kstart=kstart_b)
+    return xn0, valid, left
 
 
 def forward_fp32(model, st: StepState, compute_loss=True):
@@ -179,7 +207,7 @@ def forward_fp32(model, st: StepState, compute_loss=True):
     (``st.dev['logits']`` [B * S, V]), the shifted CE over the labelled rows and the token accuracy (``st.dev['loss_out']`` =
     [mean loss, accuracy, count, 1 / count]).  No activations are kept: there is no fp32 backward."""
     ops, geo = model.ops, model.geo
-    xn0, _, _, _ = prompt_pass_fp32(model, st)
+    xn0, _, _ = prompt_pass_fp32(model, st)
     M0, D, V = st.B * st.S, geo.llm_dim, geo.llm_vocab
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
@@ -221,7 +249,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     vc = buf("f32_vc", (L, M * ctx * W), f32)
     index, index_tmp = kv_row_index(model, B, nb, S, ctx)
     # ---- prompt pass; every layer's rotated K / V go to the cache row of the utterance's first beam
-    xn0, _, valid, left = prompt_pass_fp32(model, st, on_layer=lambda l, qkv_l: ops.f32_kv_fill(qkv_l, kc[l], vc[l], B, S, H, G, nb, ctx))
+    xn0, valid, left = prompt_pass_fp32(model, st, on_layer=lambda l, qkv_l: ops.f32_kv_fill(qkv_l, kc[l], vc[l], B, S, H, G, nb, ctx))
     if not left:
         raise ValueError("fp32 decode expects left-padded prompts (what the reference's inference collator builds)")
     kstart, last_rows = prompt_rows(model, B, S, nb, valid)
@@ -250,7 +278,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
         ops.rope_table(bs.next_pos, cos, sin, HD, geo.rope_theta)
         ops.f32_rmsnorm(x, llm.layers[0]["ln1"], xn, M, D, geo.rms_eps)
         for l in range(L):
-            _layer_fp32(model, l, x, xn, qkv, ao, gu, act, M, cos, sin, attend_cache, ws, cache=(kcv[l], vcv[l], bs.next_slot), ctx=ctx, frag=frag)
+            _layer_fp32(model, l, x, x, x, xn, qkv, ao, gu, act, M, cos, sin, attend_cache, ws, cache=(kcv[l], vcv[l], bs.next_slot), ctx=ctx, frag=frag)
         ops.f32_gemm(xn, head, logits, M, V, D, ws=ws)                                 # xn: the final norm, from the last layer's finisher
         ops.f32_logprob_topk(logits, M, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
         ops.beam_update(tv, ti, bs, False)

@@ -93,27 +93,30 @@ class EncoderWeights:
 QUERY_ROWS = (0, 1, 2, 2)   # language, event, emotion, textnorm query ids (ps-slm.py:430-442)
 
 
+def _stage_input(model, feats, feat_lens):
+    """Both encoder passes' input: [query rows | features] in enc_x0 [B, T + 4, F] (host-side concat is plumbing: 18 MB H2D per 16
+    utterances, like the reference) and the lengths + 4.  Returns (x0, lengths host int64 [B], lengths int32 device [B])."""
+    B = feats.shape[0]
+    x0 = model._buf("enc_x0", (B, feats.shape[1] + 4, feats.shape[2]), torch.float32)
+    x0[:, :4].copy_(model.encoder.embed[list(QUERY_ROWS)].unsqueeze(0).expand(B, -1, -1))
+    x0[:, 4:].copy_(feats.to(model.device, torch.float32, non_blocking=True))
+    lens_h = (np.asarray(feat_lens.cpu() if isinstance(feat_lens, torch.Tensor) else feat_lens).astype(np.int64) + 4)
+    return x0, lens_h, model._upload("enc_lens", lens_h.astype(np.int32))
+
+
 def encoder_posterior(model, feats, feat_lens, want_post=True):
     """feats [B, T, F] float (host or device), feat_lens [B].  Returns (post fp32 [B*Te, Kp] device, Te, lens int32
     device [B]) where row b*Te + 4 + t is frame t of utterance b (first 4 rows = query tokens).  ``want_post=False`` (the
     training / decode step): the CTC head's bf16 LOGITS [B*Te, Kp] are returned instead -- PSD works from them
     (psd_on_device(logits=True)) and the fp32 posterior of all frames (808 MB per 16 x 504 frames) is never written."""
-    ops, geo, enc, dev = model.ops, model.geo, model.encoder, model.device
+    ops, geo, enc = model.ops, model.geo, model.encoder
     if enc is None:
         raise RuntimeError("the audio path needs encoder weights (model_factory(..., with_encoder=True) or encoder_path)")
-    B, T, Fd = feats.shape
-    E, Hh, Ff, V = geo.enc_dim, geo.enc_heads, geo.enc_ffn, geo.ctc_vocab
-    Te, Kp = T + 4, rup(V, 64)
+    B, T, _ = feats.shape
+    Te, Kp = T + 4, rup(geo.ctc_vocab, 64)
     M = B * Te
     Spad = rup(Te, 64)
-    f32, bf = torch.float32, torch.bfloat16
-    buf = model._buf
-    # [query rows | features]: host-side concat is plumbing (18 MB H2D per 16 utterances, like the reference)
-    x0 = buf("enc_x0", (B, Te, Fd), f32)
-    x0[:, :4].copy_(enc.embed[list(QUERY_ROWS)].unsqueeze(0).expand(B, -1, -1))
-    x0[:, 4:].copy_(feats.to(dev, f32, non_blocking=True))
-    lens_h = (np.asarray(feat_lens.cpu() if isinstance(feat_lens, torch.Tensor) else feat_lens).astype(np.int64) + 4)
-    lens = model._upload("enc_lens", lens_h.astype(np.int32))
+    x0, lens_h, lens = _stage_input(model, feats, feat_lens)
     km = np.zeros((B, Spad), dtype=np.uint8)
     for b in range(B):
         km[b, : int(lens_h[b])] = 1
@@ -125,8 +128,8 @@ def encoder_posterior(model, feats, feat_lens, want_post=True):
         model.graphed_region(("encoder", B, T, bool(want_post)),
                              lambda: out.update(post=_encoder_body(model, x0, lens, key_mask, B, T, want_post)))
     if not want_post:
-        return model._buf("enc_ctc_logits", (M, Kp), bf), Te, lens
-    return model._buf("enc_post", (M, Kp), f32), Te, lens
+        return model._buf("enc_ctc_logits", (M, Kp), torch.bfloat16), Te, lens
+    return model._buf("enc_post", (M, Kp), torch.float32), Te, lens
 
 
 def _encoder_body(model, x0, lens, key_mask, B, T, want_post=True):
@@ -194,7 +197,7 @@ def encoder_posterior_fp32(model, feats, feat_lens):
     SenseVoiceEncoderSmall.forward without autocast, Multitask/model/ps-slm.py:430-454 under inference_batch.py:113-117): fp32
     LayerNorms, fp32 GEMMs (tasu_f32_gemm_nt on fp32 copies of the weights), fp32 bidirectional attention and FSMN (csrc/fp32.hip).
     Returns (posterior fp32 [B * Te, Kp], Te, lens int32 device [B]) like encoder_posterior(want_post=True)."""
-    ops, geo, enc, dev = model.ops, model.geo, model.encoder, model.device
+    ops, geo, enc = model.ops, model.geo, model.encoder
     if enc is None or not enc.keep_f32:
         raise RuntimeError("fp32 audio decode needs the encoder's fp32 weight copies (train_config.use_fp16=false before loading)")
     B, T, Fd = feats.shape
@@ -203,11 +206,7 @@ def encoder_posterior_fp32(model, feats, feat_lens):
     M = B * Te
     f32 = torch.float32
     buf = model._buf
-    x0 = buf("enc_x0", (B, Te, Fd), f32)
-    x0[:, :4].copy_(enc.embed[list(QUERY_ROWS)].unsqueeze(0).expand(B, -1, -1))
-    x0[:, 4:].copy_(feats.to(dev, f32, non_blocking=True))
-    lens_h = (np.asarray(feat_lens.cpu() if isinstance(feat_lens, torch.Tensor) else feat_lens).astype(np.int64) + 4)
-    lens = model._upload("enc_lens", lens_h.astype(np.int32))
+    x0, _, lens = _stage_input(model, feats, feat_lens)
     from .decode_fp32 import _gemm_ws
     ws = _gemm_ws(model)                     # (one size for every fp32 caller: the workspace and the K-split plans never change)
     x = buf("enc_x", (M, Fd), f32)

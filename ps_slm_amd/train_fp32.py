@@ -4,8 +4,8 @@ Multitask/scripts/finetune_deespeed_sensevoice.sh:37 -- forward and backward out
 
   forward   posterior -> LayerNorm -> Linear -> SiLU -> Linear (fp32 masters) -> embedding merge -> 28 x [RMSNorm, q|k|v + bias + RoPE,
             causal attention, o + residual, RMSNorm, gate|up, SwiGLU, down + residual] -> RMSNorm -> lm_head -> shifted CE
-            (decode_fp32's prompt pass with the activations of every layer kept: residual stream, rotated q|k|v, attention output,
-            gate|up)
+            (decode_fp32.prompt_pass_fp32, the one fp32 decoder forward, with ``keep``: the activations of every layer kept --
+            residual stream, rotated q|k|v, attention output, gate|up -- and the projector's LayerNorm statistics and pre-SiLU rows)
   backward  dlogits (written by the CE kernel over the logits) -> lm_head dgrad -> 28 x [MLP, attention] dgrad through the frozen
             decoder (tasu_f32_gemm_nt on transposed fp32 weight copies; csrc/fp32_train.hip for RMSNorm / SwiGLU / attention / RoPE
             backward; attention probabilities are recomputed from the saved q|k|v) -> the audio rows' gradient -> projector weight
@@ -15,10 +15,9 @@ A correctness mode: ~10x slower than the bf16 step at Qwen2.5-1.5B (271 against 
 real reference's fp32 goldens (loss within 2e-5, projector gradients within 2e-4 relative L2: tests/test_gpu_model.py).  Decoder weights stay
 frozen (dgrad only), like the bf16 step; LoRA and the non-default projectors train on the bf16 path only.
 """
-import numpy as np
 import torch
 
-from .decode_fp32 import F32_MAX_CTX, _gemm_ws, _need_f32
+from .decode_fp32 import _gemm_ws, prompt_pass_fp32
 from .model import HD, StepState, rup
 
 
@@ -35,68 +34,27 @@ def _transposed_weights(model):
 
 
 def forward_train_fp32(model, st: StepState):
-    """Forward of the training step in fp32 with everything the backward needs kept in ``st.dev``; loss / accuracy in
-    ``st.dev['loss_out']`` like the bf16 step; ``st.fp32 = True`` routes ``TasuModel.run_backward`` to ``backward_fp32``."""
+    """Forward of the training step in fp32: the shared prompt pass with everything the backward needs kept in ``st.dev['f32t']``,
+    then the Vp-wide logits with the CE gradient written over them; loss / accuracy in ``st.dev['loss_out']`` like the bf16 step;
+    ``st.fp32 = True`` routes ``TasuModel.run_backward`` to ``backward_fp32``."""
     ops, geo, llm, pr = model.ops, model.geo, model.llm, model.proj
-    _need_f32(model)
     if pr.kind != "linear-silu":
         raise NotImplementedError(f"the fp32 training step serves the shipped projector (linear-silu), not {pr.kind!r}")
-    B, S, M = st.B, st.S, st.M
-    if S > F32_MAX_CTX:
-        raise ValueError(f"sequence length {S} exceeds the fp32 attention's limit {F32_MAX_CTX}")
-    km = np.asarray(st.plan.key_mask)[:, :S].astype(bool)
-    valid = km.sum(1).astype(np.int64)
-    left = all(km[b, S - valid[b]:].all() for b in range(B))
-    if not (left or all(km[b, :valid[b]].all() for b in range(B))):
-        raise ValueError("the fp32 path expects every row's padding on one side")
-    D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
-    LDQ, Vp = (H + 2 * G) * HD, rup(V, 64)
-    scale = HD ** -0.5
+    if model.lora is not None:                 # (the shared layers read the merged W + s B A; the backward's transposes are the base's)
+        raise NotImplementedError("the fp32 training step serves the frozen decoder without LoRA: an adapted model trains on the bf16 path")
+    M, D, V = st.M, geo.llm_dim, geo.llm_vocab
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
-    ws = _gemm_ws(model)
-    # ---- projector (EncoderProjectorLinearSiLU, projector.py:128-151) with its intermediates kept
-    Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
-    if "post" not in d:
-        post = buf("post", (Fap, Kp), f32)
-        ops.posterior_build(d["post_ids"], d["post_alpha"], post, Fap, K)
-        d["post"] = post
-    xn_p = buf("f32t_xn_p", (Fap, Kp), f32)
-    mean, rstd = buf("ln_mean", (Fap,), f32), buf("ln_rstd", (Fap,), f32)
-    ops.layernorm_fwd(d["post"], pr.view(pr.p, "norm.weight"), pr.view(pr.p, "norm.bias"), xn_p, mean, rstd, Fap, K, geo.ln_eps)
-    h_pre, h = buf("f32t_h_pre", (Rap, Hb), f32), buf("f32t_h", (Rap, Hb), f32)
-    ops.f32_gemm(xn_p, pr.view(pr.p, pr.n_w1), h_pre, Rap, Hb, Kp, bias=pr.view(pr.p, pr.n_b1), ws=ws)
-    ops.f32_silu(h_pre, h)
-    y2 = buf("f32t_y2", (Rap, Do), f32)
-    ops.f32_gemm(h, pr.view(pr.p, pr.n_w2), y2, Rap, Do, Hb, bias=pr.view(pr.p, pr.n_b2), ws=ws)
-    # ---- decoder
-    kstart = model._upload("f32_kstart_b", ((S - valid) if left else np.zeros(B, dtype=np.int64)).astype(np.int32))
-    xs = buf("f32t_xs", (2 * L + 1, M, D), f32)                  # x_in[l] = xs[2l], x_mid[l] = xs[2l + 1], final = xs[2L]
-    qkvs, aos = buf("f32t_qkv", (L, M, LDQ), f32), buf("f32t_ao", (L, M, H * HD), f32)
-    gus = buf("f32t_gu", (L, M, 2 * I), f32)
-    xn, act = buf("f32t_xn", (M, D), f32), buf("f32t_act", (M, I), f32)
-    cos, sin = buf("f32_cos0", (M, HD // 2), f32), buf("f32_sin0", (M, HD // 2), f32)
-    ops.f32_embed_merge(llm.embed, y2, d["kind"], d["idx"], xs[0], M, D)
-    ops.rope_table(d["pos"], cos, sin, HD, geo.rope_theta)
-    ops.f32_rmsnorm(xs[0], llm.layers[0]["ln1"], xn, M, D, geo.rms_eps)
-    for l in range(L):
-        f, w = llm.f32["layers"][l], llm.layers[l]
-        next_norm = llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm
-        ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkvs[l], cos, sin, M, H, G, D, ws)
-        ops.f32_attn_prefill(qkvs[l], kstart, aos[l], B, S, H, G, scale)
-        ops.f32_gemm_resid_rmsnorm(aos[l], f["wo"], xs[2 * l + 1], w["ln2"], xn, M, D, H * HD, geo.rms_eps, ws, resid=xs[2 * l])
-        ops.f32_gemm(xn, f["wgu"], gus[l], M, 2 * I, D, ws=ws)       # (gate|up is kept for the backward: not the fused finisher)
-        ops.f32_swiglu(gus[l], act, M, I)
-        ops.f32_gemm_resid_rmsnorm(act, f["wd"], xs[2 * l + 2], next_norm, xn, M, D, I, geo.rms_eps, ws, resid=xs[2 * l + 1])
+    keep = {}
+    xn, _, _ = prompt_pass_fp32(model, st, keep=keep)
     # ---- loss head: logits for every position (pad columns zeroed once: the lm_head dgrad contracts over Vp), CE + its gradient
-    logits = buf("f32t_logits", (M, Vp), f32)
-    ops.f32_gemm(xn, llm.f32["head"], logits, M, V, D, ws=ws)
+    logits = buf("f32t_logits", (M, rup(V, 64)), f32)
+    ops.f32_gemm(xn, llm.f32["head"], logits, M, V, D, ws=_gemm_ws(model))
     row_loss, row_hit = buf("row_loss", (M,), f32), buf("row_hit", (M,), i32)
     ops.f32_ce(logits, d["shift_labels"], M, V, row_loss, row_hit, dlogits=logits, inv_count=d["inv_count"])   # dlogits in place
     res = buf("loss_out", (4,), f32)
     ops.ce_reduce(row_loss, row_hit, d["shift_labels"], M, res)
-    d.update(loss_out=res, f32t=dict(xs=xs, qkvs=qkvs, aos=aos, gus=gus, cos=cos, sin=sin, kstart=kstart, dlogits=logits, xn_p=xn_p, h_pre=h_pre,
-                                     h=h, mean=mean, rstd=rstd))
+    d.update(loss_out=res, f32t=dict(keep, dlogits=logits))
     d.pop("logits", None)
     st.fp32 = True
 

@@ -646,3 +646,50 @@ def test_effective_min_length_is_hfs_under_inputs_embeds():
     assert not bs.ban_eos()                                                    # the reference's default (and any min_length <= S): never banned
     bs = BeamState(1, 2, 8, eos=9, pad=9, min_length=effective_min_length(23, 20))
     assert bs.ban_eos() and bs.min_length == 3
+
+
+def test_fp32_entry_points_check_their_inputs_before_any_fp32_launch(mid):
+    """The fp32 training step, eval forward and generate() refuse a prompt padded on both sides and S > 2048 (ValueError), and a
+    model without fp32 weight copies (RuntimeError); the training step also refuses a LoRA model and a projector other than
+    linear-silu (NotImplementedError).  FakeOps has no f32_* kernels, so each must raise before the first fp32 launch."""
+    from ps_slm_amd.decode_fp32 import beam_search_generate_fp32, forward_fp32
+    from ps_slm_amd.lora import LoraConfig
+    from ps_slm_amd.train_fp32 import forward_train_fp32
+    geo, sd = mid
+    entries = [forward_train_fp32, forward_fp32, lambda m, st: beam_search_generate_fp32(m, st, num_beams=4, max_new_tokens=4)]
+
+    def model(geo=geo, sd=sd, keep_f32=True):
+        m = TasuModel(geo, FakeOps(), "cpu")
+        m.llm.keep_f32 = keep_f32
+        m.load_reference_state_dict(sd)
+        return m
+
+    def state(m, prompt_len=9):
+        b = synthetic_text_batch(m.geo, 3, seed=3, prompt_len=prompt_len, n_audio=21, target_len=17, speech_pos=4, feat_frames=12,
+                                 noise=False, ragged=True)
+        return m.prepare_text(b["input_ids"], b["attention_mask"], b["labels"], b["post_ids"], None, None)
+
+    m = model()
+    for fn in entries:
+        st = state(m)
+        km = st.plan.key_mask.copy()
+        km[0, 0] = km[0, st.S - 1] = 0                       # row 0 padded at both ends
+        st.plan.key_mask = km
+        with pytest.raises(ValueError, match="one side"):
+            fn(m, st)
+        st = state(m, prompt_len=2048)
+        assert st.S > 2048
+        with pytest.raises(ValueError, match="2048"):
+            fn(m, st)
+    m = model(keep_f32=False)
+    for fn in entries:
+        with pytest.raises(RuntimeError, match="fp32 copies"):
+            fn(m, state(m))
+    m = model()
+    m.enable_lora(LoraConfig(r=8, lora_alpha=16.0, lora_dropout=0.0))
+    with pytest.raises(NotImplementedError, match="LoRA"):
+        forward_train_fp32(m, state(m))
+    geo2 = Geometry.from_dict(dict(MID_GEOMETRY, projector="linear", projector_ds_rate=2))
+    m = model(geo2, random_state_dict(geo2, 7, with_encoder=False))
+    with pytest.raises(NotImplementedError, match="linear-silu"):
+        forward_train_fp32(m, state(m))

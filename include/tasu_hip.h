@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 17
+#define TASU_ABI_VERSION 18
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -730,6 +730,20 @@ int tasu_f32_ce(const float* logits, int ld, const int32_t* shift_labels, int M,
 int tasu_f32_ca_attn(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, int R,
                      float* workspace, int64_t workspace_floats, void* stream);
 int64_t tasu_f32_ca_workspace_floats(int R, int V, int D, int H);
+/* The same forward for the TRAINING step (projector.py:111-126 under autograd): also writes lse[R, H], the log-sum-exp of every
+ * (row, head)'s scaled scores, which tasu_f32_ca_attn_bwd reads.  `out` is tasu_f32_ca_attn's bit for bit; same checks.            */
+int tasu_f32_ca_attn_lse(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, float* lse,
+                         int R, float* workspace, int64_t workspace_floats, void* stream);
+/* Backward of that attention with respect to q (what autograd derives for projector.py:117-125; keys and values are the frozen
+ * embedding table, so dq is the only gradient): with out / lse of tasu_f32_ca_attn_lse and dout [R, D] (row pitch lddo),
+ *   delta[r, h] = sum_c dout[r, h, c] out[r, h, c],   P = exp(q_h table_h^T / denom - lse),   dP = dout_h table_h^T,
+ *   dq[r, h] = (P . (dP - delta)) table_h / denom
+ * over all V rows, fused like the forward (csrc/f32_ca.hip): scores recomputed from LDS-staged key tiles on v_mfma_f32_16x16x4_f32, no
+ * [R, V] buffer, the forward's V-splits, their partial dq added in ascending split order (deterministic).  Same shape rules and
+ * workspace size as the forward; additionally lddo, lddq >= D, lddo % 4 == 0, dout 16-byte aligned.  TASU_ERR_ARG before any launch. */
+int tasu_f32_ca_attn_bwd(const float* q, int ldq, const float* table, int V, int D, int H, float denom, const float* out, int ldo,
+                         const float* dout, int lddo, const float* lse, float* dq, int lddq, int R, float* workspace,
+                         int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------ fp32 training step (backward)
  * train_config.use_fp16 = false DURING TRAINING (the shipped recipe, Multitask/scripts/finetune_deespeed_sensevoice.sh:37: forward and
@@ -739,6 +753,10 @@ int64_t tasu_f32_ca_workspace_floats(int R, int V, int D, int H);
  *   tasu_f32_rmsnorm_bwd            dx (+)= rstd (w . dy) - x rstd^3 / D sum(w dy x)            (modeling_qwen2.py:41-48 differentiated)
  *   tasu_f32_swiglu_bwd             dgu[M, 2I] from dact[M, I] and the saved gate|up
  *   tasu_f32_silu                   out = silu(x) (dy NULL) or dy * silu'(x)
+ *   tasu_f32_relu_bwd               out = dy where y > 0, else 0: nn.ReLU of projector.py:42,64,66 differentiated (y: its output or input)
+ *   tasu_f32_lora_dropout           out[M, C] = [out +] x * keep / (1 - p): peft's lora_dropout (nn.Dropout on the adapter's input of
+ *                                   lora.Linear.forward) and its backward in fp32, the counter-based mask of tasu_lora_dropout
+ *                                   (element m * C + c of stream_id at rng = {seed, step}); p = 0 copies / accumulates
  *   tasu_f32_colsum                 out[c] = sum_r x[r, c]
  *   tasu_f32_layernorm_bwd_params   dgamma / dbeta of the projector's LayerNorm from an fp32 dy (tasu_layernorm_bwd_params)
  *   tasu_f32_transpose              dst[c, r] = src[r, c], rows [R, Rpad) zero
@@ -749,6 +767,9 @@ int64_t tasu_f32_ca_workspace_floats(int R, int V, int D, int H);
 int tasu_f32_rmsnorm_bwd(const float* dy, const float* x, const float* w, float* dx, int M, int D, float eps, int accumulate, void* stream);
 int tasu_f32_swiglu_bwd(const float* dact, const float* gu, float* dgu, int M, int I, void* stream);
 int tasu_f32_silu(const float* x, const float* dy, float* out, int64_t n, void* stream);
+int tasu_f32_relu_bwd(const float* y, const float* dy, float* out, int64_t n, void* stream);
+int tasu_f32_lora_dropout(const float* x, int ldx, float* out, int ldo, int M, int C, float p, const void* rng, int stream_id,
+                          int accumulate, void* stream);
 int tasu_f32_colsum(const float* x, int ld, float* out, int R, int C, void* stream);
 int tasu_f32_layernorm_bwd_params(const float* dy, int lddy, const float* x, int ldx, const float* mean, const float* rstd, float* dgamma,
                                   float* dbeta, int R, int D, void* stream);

@@ -152,10 +152,14 @@ PROTOTYPES.update({
     "tasu_f32_ce": [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "tasu_f32_ca_attn": [vp, i32, vp, i32, i32, i32, f32, vp, i32, i32, vp, i64, vp],
     "tasu_f32_ca_workspace_floats": [i32, i32, i32, i32],
+    "tasu_f32_ca_attn_lse": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp, i32, vp, i64, vp],
+    "tasu_f32_ca_attn_bwd": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp, i32, vp, vp, i32, i32, vp, i64, vp],
     # fp32 training step: backward kernels (csrc/fp32_train.hip)
     "tasu_f32_rmsnorm_bwd": [vp, vp, vp, vp, i32, i32, f32, i32, vp],
     "tasu_f32_swiglu_bwd": [vp, vp, vp, i32, i32, vp],
     "tasu_f32_silu": [vp, vp, vp, i64, vp],
+    "tasu_f32_relu_bwd": [vp, vp, vp, i64, vp],
+    "tasu_f32_lora_dropout": [vp, i32, vp, i32, i32, i32, f32, vp, i32, i32, vp],
     "tasu_f32_colsum": [vp, i32, vp, i32, i32, vp],
     "tasu_f32_layernorm_bwd_params": [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp],
     "tasu_f32_transpose": [vp, i32, vp, i32, i32, i32, i32, vp],
@@ -163,7 +167,7 @@ PROTOTYPES.update({
     "tasu_f32_attn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
 })
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

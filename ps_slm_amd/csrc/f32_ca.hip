@@ -34,6 +34,10 @@ struct Cfg {
   static size_t lds_bytes(int dh) {
     return sizeof(float) * ((size_t)ROWS * (dh + 4) + (size_t)KT * (dh + 4) + (size_t)PARTS * ROWS * SLD + 3 * ROWS);
   }
+  // backward: Q and dO tiles, one key tile, the score tile and the dP tile, lse and delta per row (136-151 KiB of the CU's 160)
+  static size_t bwd_lds_bytes(int dh) {
+    return sizeof(float) * (2 * (size_t)ROWS * (dh + 4) + (size_t)KT * (dh + 4) + 2 * (size_t)PARTS * ROWS * SLD + 2 * ROWS);
+  }
 };
 
 inline int cfg_of(int dh) { return dh <= 128 ? 0 : (dh <= 256 ? 1 : 2); }
@@ -214,8 +218,9 @@ __global__ __launch_bounds__(NT) void f32_ca_attn_kernel(const float* __restrict
 }
 
 // out[r, c] = sum_z exp(m_z - M) O_z[r, c] / sum_z exp(m_z - M) l_z, splits in ascending order
+// lse (optional): [R, H] = M + log(L), what the backward's P = exp(S - lse) reads; `out` does not depend on it
 __global__ __launch_bounds__(256) void f32_ca_merge_kernel(const float* __restrict__ ws, int splits, float* __restrict__ out, int ldo,
-                                                          int R, int D, int H, int dh) {
+                                                          int R, int D, int H, int dh, float* __restrict__ lse) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)R * D) return;
   const int r = (int)(i / D), c = (int)(i - (size_t)r * D), h = c / dh;
@@ -230,6 +235,177 @@ __global__ __launch_bounds__(256) void f32_ca_merge_kernel(const float* __restri
     acc += ws[((size_t)z * R + r) * D + c] * w;
   }
   out[(size_t)r * ldo + c] = acc / L;
+  if (lse && c == h * dh) lse[(size_t)r * H + h] = M + logf(L);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ backward
+// dq of the same attention (keys = values = the frozen table: the only gradient is the query's).  Same tiling, same V-splits and
+// the same key-tile staging as the forward; per key tile, with lse from the forward and delta[r] = sum_c dO[r, c] O[r, c] of the head:
+//   S = Q K^T / denom (recomputed),  P = exp(S - lse),  dP = dO K^T,  dS = P (dP - delta) / denom,  dq += dS K
+// S and dP come out of one sweep over the key tile in LDS (two accumulator pairs per 16 x 16 tile); dS overwrites S and feeds the
+// third product exactly as P feeds O in the forward.  Each split writes its partial dq to the workspace [splits][R][D];
+// f32_ca_bwd_merge_kernel adds the splits in ascending order.
+template <int RT, int KT>
+__global__ __launch_bounds__(NT) void f32_ca_attn_bwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ E, int V, int D,
+                                                            int dh, float denom, const float* __restrict__ out, int ldo,
+                                                            const float* __restrict__ dout, int lddo, const float* __restrict__ lse,
+                                                            float* __restrict__ ws, int R, int tiles_per_split, int n_tiles) {
+  using C = Cfg<RT, KT>;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int ldk = dh + 4;
+  float* sQ = lds;                                    // [ROWS][dh + 4]
+  float* sG = sQ + C::ROWS * ldk;                     // [ROWS][dh + 4]: dO
+  float* sK = sG + C::ROWS * ldk;                     // [KT][dh + 4]
+  float* sS = sK + KT * ldk;                          // [PARTS][ROWS][SLD]: scores, then dS (part 0)
+  float* sP = sS + C::PARTS * C::ROWS * C::SLD;       // [PARTS][ROWS][SLD]: dP
+  float* sL = sP + C::PARTS * C::ROWS * C::SLD;       // lse, delta per row
+  float* sD = sL + C::ROWS;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, g = lane >> 4, l16 = lane & 15;
+  const int r0 = blockIdx.x * C::ROWS, h = blockIdx.y, z = blockIdx.z, c0 = h * dh;
+  const int tile_lo = z * tiles_per_split, tile_hi = min(n_tiles, tile_lo + tiles_per_split);
+  const int dq = dh / 4, nh = dh / 16;
+  constexpr int TPR = NT / C::ROWS, KPT = KT / TPR;
+  const int srow = t / TPR, sidx = t % TPR;
+  // ---- Q and dO tiles (rows >= R zero), lse, delta
+  for (int i = t; i < C::ROWS * dq; i += NT) {
+    const int r = i / dq, c = (i - r * dq) * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f}, w = {0.f, 0.f, 0.f, 0.f};
+    if (r0 + r < R) {
+      v = *(const f32x4*)(q + (size_t)(r0 + r) * ldq + c0 + c);
+      w = *(const f32x4*)(dout + (size_t)(r0 + r) * lddo + c0 + c);
+    }
+    *(f32x4*)&sQ[r * ldk + c] = v;
+    *(f32x4*)&sG[r * ldk + c] = w;
+  }
+  {
+    float dl = 0.f;
+    if (r0 + srow < R)
+      for (int c = sidx; c < dh; c += TPR) dl += dout[(size_t)(r0 + srow) * lddo + c0 + c] * out[(size_t)(r0 + srow) * ldo + c0 + c];
+#pragma unroll
+    for (int off = 1; off < TPR; off <<= 1) dl += __shfl_xor(dl, off, 64);
+    if (sidx == 0) {
+      sD[srow] = dl;
+      sL[srow] = r0 + srow < R ? lse[(size_t)(r0 + srow) * gridDim.y + h] : 0.f;
+    }
+  }
+  f32x4 kr[C::LPW];
+  auto load_tile = [&](int tile) {
+    const int k0 = tile * KT;
+#pragma unroll
+    for (int j = 0; j < C::LPW; ++j) {
+      const int i = t + j * NT;
+      kr[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (i < KT * dq) {
+        const int k = i / dq, c = (i - k * dq) * 4;
+        if (k0 + k < V) kr[j] = *(const f32x4*)(E + (size_t)(k0 + k) * D + c0 + c);
+      }
+    }
+  };
+  auto store_tile = [&]() {
+#pragma unroll
+    for (int j = 0; j < C::LPW; ++j) {
+      const int i = t + j * NT;
+      if (i < KT * dq) {
+        const int k = i / dq, c = (i - k * dq) * 4;
+        *(f32x4*)&sK[k * ldk + c] = kr[j];
+      }
+    }
+  };
+  f32x4 o[C::OPW];
+#pragma unroll
+  for (int j = 0; j < C::OPW; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int n_otiles = RT * nh;
+  const int part = wave % C::PARTS, pw = wave / C::PARTS;
+  const int h_lo = part * nh / C::PARTS, h_hi = (part + 1) * nh / C::PARTS;
+
+  if (tile_lo < tile_hi) load_tile(tile_lo);
+  for (int tile = tile_lo; tile < tile_hi; ++tile) {
+    store_tile();
+    __syncthreads();                                                   // (A) key tile, Q, dO and the row statistics in LDS
+    if (tile + 1 < tile_hi) load_tile(tile + 1);
+    // ---- S = Q K^T and dP = dO K^T over the same key fragments
+#pragma unroll
+    for (int pp = 0; pp < C::PPW; ++pp) {
+      const int p = pw * C::PPW + pp, rt = p / (KT / 16), kt = p % (KT / 16);
+      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f}, b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
+      const float* kp = sK + (kt * 16 + l16) * ldk + 4 * g;
+      const float* qp = sQ + (rt * 16 + l16) * ldk + 4 * g;
+      const float* gp = sG + (rt * 16 + l16) * ldk + 4 * g;
+      int hh = h_lo;
+      for (; hh + 1 < h_hi; hh += 2) {
+        const f32x4 fk0 = *(const f32x4*)(kp + hh * 16), fq0 = *(const f32x4*)(qp + hh * 16), fg0 = *(const f32x4*)(gp + hh * 16);
+        const f32x4 fk1 = *(const f32x4*)(kp + hh * 16 + 16), fq1 = *(const f32x4*)(qp + hh * 16 + 16), fg1 = *(const f32x4*)(gp + hh * 16 + 16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          a0 = mfma4(fk0[e], fq0[e], a0), a1 = mfma4(fk1[e], fq1[e], a1);
+          b0 = mfma4(fk0[e], fg0[e], b0), b1 = mfma4(fk1[e], fg1[e], b1);
+        }
+      }
+      if (hh < h_hi) {
+        const f32x4 fk0 = *(const f32x4*)(kp + hh * 16), fq0 = *(const f32x4*)(qp + hh * 16), fg0 = *(const f32x4*)(gp + hh * 16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a0 = mfma4(fk0[e], fq0[e], a0), b0 = mfma4(fk0[e], fg0[e], b0);
+      }
+      const int at = (part * C::ROWS + rt * 16 + l16) * C::SLD + kt * 16 + 4 * g;
+      *(f32x4*)&sS[at] = a0 + a1;
+      *(f32x4*)&sP[at] = b0 + b1;
+    }
+    __syncthreads();                                                   // (B) S and dP in LDS
+    // ---- dS = P (dP - delta) / denom over this tile's keys (the parts' partial sums added in part order); keys >= V: 0
+    {
+      const int kbase = tile * KT;
+      const float l = sL[srow], dl = sD[srow];
+#pragma unroll
+      for (int j = 0; j < KPT; ++j) {
+        const int k = sidx * KPT + j;
+        float v = sS[srow * C::SLD + k], dp = sP[srow * C::SLD + k];
+#pragma unroll
+        for (int pt = 1; pt < C::PARTS; ++pt) v += sS[(pt * C::ROWS + srow) * C::SLD + k], dp += sP[(pt * C::ROWS + srow) * C::SLD + k];
+        v = v / denom;
+        sS[srow * C::SLD + k] = kbase + k < V ? expf(v - l) * (dp - dl) / denom : 0.f;
+      }
+    }
+    __syncthreads();                                                   // (C) dS in LDS
+    // ---- dq += dS K, the tile's contribution summed on its own and added once (as the forward's O)
+#pragma unroll
+    for (int j = 0; j < C::OPW; ++j) {
+      const int ot = wave + j * NW;
+      if (ot < n_otiles) {
+        const int rt = ot / nh, ct = ot - rt * nh;
+        const float* pp = sS + (rt * 16 + l16) * C::SLD + 4 * g;
+        const float* vp = sK + (4 * g) * ldk + ct * 16 + l16;
+        f32x4 tp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kh = 0; kh < KT / 16; ++kh) {
+          const f32x4 fp = *(const f32x4*)(pp + kh * 16);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) tp = mfma4(vp[(kh * 16 + e) * ldk], fp[e], tp);
+        }
+        o[j] = o[j] + tp;
+      }
+    }
+    __syncthreads();                                                   // (D) LDS free for the next tile
+  }
+  float* wo = ws + (size_t)z * R * D;
+#pragma unroll
+  for (int j = 0; j < C::OPW; ++j) {
+    const int ot = wave + j * NW;
+    if (ot < n_otiles) {
+      const int rt = ot / nh, ct = ot - rt * nh, r = r0 + rt * 16 + l16;
+      if (r < R) *(f32x4*)(wo + (size_t)r * D + c0 + ct * 16 + 4 * g) = o[j];
+    }
+  }
+}
+
+// dq[r, c] = sum_z ws[z][r][c], splits in ascending order
+__global__ __launch_bounds__(256) void f32_ca_bwd_merge_kernel(const float* __restrict__ ws, int splits, float* __restrict__ dq, int lddq,
+                                                              int R, int D) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)R * D) return;
+  const int r = (int)(i / D), c = (int)(i - (size_t)r * D);
+  float acc = 0.f;
+  for (int z = 0; z < splits; ++z) acc += ws[((size_t)z * R + r) * D + c];
+  dq[(size_t)r * lddq + c] = acc;
 }
 
 template <int RT, int KT>
@@ -249,6 +425,24 @@ static int launch(const float* q, int ldq, const float* E, int V, int D, int H, 
   return TASU_OK;
 }
 
+template <int RT, int KT>
+static int launch_bwd(const float* q, int ldq, const float* E, int V, int D, int H, float denom, const float* out, int ldo,
+                      const float* dout, int lddo, const float* lse, float* ws, int R, int splits, int per, hipStream_t st) {
+  using C = Cfg<RT, KT>;
+  const int dh = D / H, n_tiles = (V + KT - 1) / KT;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)f32_ca_attn_bwd_kernel<RT, KT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)C::bwd_lds_bytes(C::DH_MAX)) != hipSuccess)
+      return TASU_ERR_LAUNCH;
+    attr = true;
+  }
+  dim3 grid((R + C::ROWS - 1) / C::ROWS, H, splits);
+  TASU_LAUNCH((f32_ca_attn_bwd_kernel<RT, KT>), grid, dim3(NT), C::bwd_lds_bytes(dh), st, q, ldq, E, V, D, dh, denom, out, ldo, dout, lddo,
+              lse, ws, R, per, n_tiles);
+  return TASU_OK;
+}
+
 }  // namespace tasu_f32_ca
 
 using namespace tasu_f32_ca;
@@ -259,8 +453,8 @@ extern "C" int64_t tasu_f32_ca_workspace_floats(int R, int V, int D, int H) {
   return (int64_t)plan_splits(R, V, D, H, &per) * R * ((int64_t)D + 2 * H);
 }
 
-extern "C" int tasu_f32_ca_attn(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, int R,
-                                float* workspace, int64_t workspace_floats, void* stream) {
+static int ca_forward(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, float* lse, int R,
+                      float* workspace, int64_t workspace_floats, void* stream) {
   if (!q || !table || !out || !workspace || V < 1 || R < 1 || H < 1 || D < H || D % H) return TASU_ERR_ARG;
   const int dh = D / H;
   if (dh % 16 || dh > MAX_DH || ldq < D || ldo < D || ldq % 4 || !(denom > 0.f) || !isfinite(denom)) return TASU_ERR_ARG;
@@ -278,6 +472,42 @@ extern "C" int tasu_f32_ca_attn(const float* q, int ldq, const float* table, int
   }
   if (rc) return rc;
   const size_t n = (size_t)R * D;
-  TASU_LAUNCH(f32_ca_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, splits, out, ldo, R, D, H, dh);
+  TASU_LAUNCH(f32_ca_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, splits, out, ldo, R, D, H, dh, lse);
+  return TASU_OK;
+}
+
+extern "C" int tasu_f32_ca_attn(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo, int R,
+                                float* workspace, int64_t workspace_floats, void* stream) {
+  return ca_forward(q, ldq, table, V, D, H, denom, out, ldo, nullptr, R, workspace, workspace_floats, stream);
+}
+
+extern "C" int tasu_f32_ca_attn_lse(const float* q, int ldq, const float* table, int V, int D, int H, float denom, float* out, int ldo,
+                                    float* lse, int R, float* workspace, int64_t workspace_floats, void* stream) {
+  if (!lse) return TASU_ERR_ARG;
+  return ca_forward(q, ldq, table, V, D, H, denom, out, ldo, lse, R, workspace, workspace_floats, stream);
+}
+
+extern "C" int tasu_f32_ca_attn_bwd(const float* q, int ldq, const float* table, int V, int D, int H, float denom, const float* out, int ldo,
+                                    const float* dout, int lddo, const float* lse, float* dq, int lddq, int R, float* workspace,
+                                    int64_t workspace_floats, void* stream) {
+  if (!q || !table || !out || !dout || !lse || !dq || !workspace || V < 1 || R < 1 || H < 1 || D < H || D % H) return TASU_ERR_ARG;
+  const int dh = D / H;
+  if (dh % 16 || dh > MAX_DH || ldq < D || ldo < D || lddo < D || lddq < D || ldq % 4 || lddo % 4 || !(denom > 0.f) || !isfinite(denom))
+    return TASU_ERR_ARG;
+  if (((uintptr_t)q | (uintptr_t)table | (uintptr_t)dout | (uintptr_t)workspace) & 15) return TASU_ERR_ARG;
+  if ((int64_t)R * D > INT32_MAX || (int64_t)V * D > ((int64_t)1 << 40)) return TASU_ERR_ARG;
+  int per;
+  const int splits = plan_splits(R, V, D, H, &per);                   // the forward's splits: [splits][R][D] fits its workspace
+  if (workspace_floats < tasu_f32_ca_workspace_floats(R, V, D, H)) return TASU_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  switch (cfg_of(dh)) {
+    case 0: rc = launch_bwd<4, 64>(q, ldq, table, V, D, H, denom, out, ldo, dout, lddo, lse, workspace, R, splits, per, st); break;
+    case 1: rc = launch_bwd<2, 64>(q, ldq, table, V, D, H, denom, out, ldo, dout, lddo, lse, workspace, R, splits, per, st); break;
+    default: rc = launch_bwd<1, 32>(q, ldq, table, V, D, H, denom, out, ldo, dout, lddo, lse, workspace, R, splits, per, st); break;
+  }
+  if (rc) return rc;
+  const size_t n = (size_t)R * D;
+  TASU_LAUNCH(f32_ca_bwd_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, splits, dq, lddq, R, D);
   return TASU_OK;
 }

@@ -54,6 +54,34 @@ __global__ __launch_bounds__(256) void silu_kernel(const float* __restrict__ x, 
   out[i] = dy ? dy[i] * sg * (1.f + v * (1.f - sg)) : v * sg;
 }
 
+// dx = dy where the ReLU passed (y > 0: y is the ReLU's output, or its input -- the same mask), else 0 (projector: Linear -> ReLU)
+__global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = y[i] > 0.f ? dy[i] : 0.f;
+}
+
+// LoRA dropout in fp32 (peft's lora_dropout on the adapter's input, and its backward): out = [out +] x * keep / (1 - p) with the
+// counter-based mask of csrc/lora.hip -- element idx = m * C + c of dropout stream `sid` at micro-step rng[1] is kept iff the upper
+// 32 bits of splitmix64((seed ^ step * GOLD ^ sid << 44) + idx * ODD) are >= p * 2^32 (oracle/lora_oracle.py: lora_keep_mask) -- so
+// the fp32 step draws the masks the bf16 step draws, and its backward regenerates the forward's.
+__device__ __forceinline__ uint64_t drop_mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void lora_dropout_kernel(const float* __restrict__ x, int ldx, float* __restrict__ out, int ldo, int M, int C,
+                                                           uint32_t thr, float inv, const int64_t* __restrict__ rng, int sid, int accumulate) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)M * C) return;
+  const int m = (int)(idx / C), c = (int)(idx - (int64_t)m * C);
+  const uint64_t key = (uint64_t)rng[0] ^ ((uint64_t)rng[1] * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(uint32_t)sid << 44);
+  const uint64_t z = drop_mix64(key + (uint64_t)idx * 0xD1B54A32D192ED03ull);
+  const float v = x[(size_t)m * ldx + c] * ((uint32_t)(z >> 32) >= thr ? inv : 0.f);
+  float* o = out + (size_t)m * ldo + c;
+  *o = accumulate ? *o + v : v;
+}
+
 // out[c] = sum_r x[r, c] (bias gradients), rows in ascending order: one thread per column, coalesced over the columns
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, int ld, float* __restrict__ out, int R, int C) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -414,6 +442,24 @@ extern "C" int tasu_f32_swiglu_bwd(const float* dact, const float* gu, float* dg
 extern "C" int tasu_f32_silu(const float* x, const float* dy, float* out, int64_t n, void* stream) {
   if (!x || !out || n <= 0) return TASU_ERR_ARG;
   TASU_LAUNCH(silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, out, (size_t)n);
+  return TASU_OK;
+}
+
+extern "C" int tasu_f32_relu_bwd(const float* y, const float* dy, float* out, int64_t n, void* stream) {
+  if (!y || !dy || !out || n <= 0) return TASU_ERR_ARG;
+  TASU_LAUNCH(relu_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, dy, out, (size_t)n);
+  return TASU_OK;
+}
+
+extern "C" int tasu_f32_lora_dropout(const float* x, int ldx, float* out, int ldo, int M, int C, float p, const void* rng, int stream_id,
+                                     int accumulate, void* stream) {
+  if (!x || !out || !rng || M <= 0 || C <= 0 || ldx < C || ldo < C || stream_id < 0 || !(p >= 0.f) || !(p < 1.f)) return TASU_ERR_ARG;
+  const double t = (double)p * 4294967296.0;                          // (tasu_lora_dropout's threshold and scale)
+  const uint32_t thr = t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
+  const float inv = 1.0f / (1.0f - p);
+  const int64_t n = (int64_t)M * C;
+  TASU_LAUNCH(lora_dropout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, out, ldo, M, C, thr, inv,
+              (const int64_t*)rng, stream_id, accumulate);
   return TASU_OK;
 }
 

@@ -65,8 +65,11 @@ def project_fp32(model, st: StepState, keep=None):
     linear (EncoderProjectorConcat, :28-49): k consecutive frames as one row -> Linear -> ReLU -> Linear;
     cov1d-linear (EncoderProjectorCov1d, :53-73): Conv1d(kernel = stride = k) as one GEMM over the k-frame rows -> ReLU -> Linear ->
     ReLU -> Linear;  cross-attention (EncoderProjectorCTCCA, :104-126): Q = W_q(post), then tasu_f32_ca_attn over the fp32 input
-    embedding table.  ``keep`` (the training step, linear-silu only): the LayerNorm statistics are written and the SiLU runs on its
-    own after W1, so that the backward can read xn_p, mean, rstd, h_pre and h from it."""
+    embedding table.  ``keep`` (the training step): what backward_fp32 reads.  linear-silu: the LayerNorm statistics are written and
+    the SiLU runs on its own after W1 (xn_p, mean, rstd, h_pre, h).  linear / cov1d-linear: the same launches as without ``keep`` --
+    the k-frame rows, the conv's output c0 and h are kept AFTER their ReLU, whose output carries the mask of its input (y > 0 where
+    x > 0).  cross-attention: q, the attention's output and its per-(row, head) log-sum-exp (tasu_f32_ca_attn_lse: the same
+    ``out`` bits)."""
     ops, pr = model.ops, model.proj
     f32 = torch.float32
     Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
@@ -81,7 +84,12 @@ def project_fp32(model, st: StepState, keep=None):
         q = model._buf("f32_ca_q", (Rap, Do), f32)
         ops.f32_gemm(st.dev["post"], pr.view(pr.p, "W_q.weight"), q, Rap, Do, Kp, ws=ws)
         cws = model._buf("f32_ca_ws", (ops.f32_ca_workspace_floats(Rap, geo.llm_vocab, Do, geo.ca_heads),), f32)
-        ops.f32_ca_attn(q, model.llm.embed, y2, Rap, geo.ca_heads, ws=cws)
+        if keep is None:
+            ops.f32_ca_attn(q, model.llm.embed, y2, Rap, geo.ca_heads, ws=cws)
+        else:
+            lse = model._buf("f32t_ca_lse", (Rap, geo.ca_heads), f32)
+            ops.f32_ca_attn_lse(q, model.llm.embed, y2, lse, Rap, geo.ca_heads, ws=cws)
+            keep.update(q=q, lse=lse, out=y2, ca_ws=cws)
         st.dev["y2_f32"] = y2
         return y2
     if pr.has_norm:
@@ -96,7 +104,9 @@ def project_fp32(model, st: StepState, keep=None):
         ops.f32_gemm(x, pr.view(pr.p, "conv1d.weight"), c0, Rap, Kp, pr.k * Kp, bias=pr.view(pr.p, "conv1d.bias"), act=2, ws=ws)
         x = c0
     h = model._buf("f32_proj_h", (Rap, Hb), f32)
-    if keep is None:
+    if keep is not None and not pr.has_norm:
+        keep.update(xcat=st.dev["post"].view(Rap, pr.k * Kp), x1=x, h=h)
+    if keep is None or not pr.has_norm:
         ops.f32_gemm(x, pr.view(pr.p, pr.n_w1), h, Rap, Hb, pr.kin * Kp, bias=pr.view(pr.p, pr.n_b1), act=1 if pr.has_norm else 2, ws=ws)
     else:
         h_pre = model._buf("f32t_h_pre", (Rap, Hb), f32)
@@ -192,9 +202,12 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
             on_layer(l, qkv)
         ops.f32_attn_prefill(qkv, kstart_b, ao, B, S, H, G, scale)
 
+    layer = _layer_fp32
+    if keep is not None and model.lora is not None:        # the training step of an adapted decoder runs the adapters unmerged
+        from .train_fp32 import lora_layer_fp32 as layer
     ops.f32_rmsnorm(xs[0], llm.layers[0]["ln1"], xn0, M0, D, geo.rms_eps)
     for l in range(L):
-        _layer_fp32(model, l, xs[2 * l], xs[2 * l + 1], xs[2 * l + 2], xn0, qkvs[l], aos[l], gus[l], act0, M0, cos0, sin0, attend_prompt,
+        layer(model, l, xs[2 * l], xs[2 * l + 1], xs[2 * l + 2], xn0, qkvs[l], aos[l], gus[l], act0, M0, cos0, sin0, attend_prompt,
                     ws, keep_gu=keep is not None)
     if keep is not None:
         keep.update(xs=xs, qkvs=qkvs, aos=aos, gus=gus, cos=cos0, sin=sin0, kstart=kstart_b)

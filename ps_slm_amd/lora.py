@@ -24,7 +24,8 @@ weights (merged_llm).  DESIGN.md 4g has the measurements.
 
 use_fp16 = false: generate() and the eval-mode forward run on fp32 merged weights W_f32 + s B A (merged_llm_f32): +1x the decoder's
 fp32 layer weights, about 5 GB at Qwen2.5-1.5B, plus fragment-order copies of gate|up and down (~4.6 GB) at the first fp32 generate().
-The training step of an adapted model stays on the bf16 path above.
+The training step of an adapted model stays on the bf16 path above unless train_config.mixed_precision = false asks for fp32
+everywhere: then it runs unmerged in fp32 (ps_slm_amd/train_fp32.py: LoraF32), with the dropout masks of this path.
 """
 import math
 from dataclasses import dataclass

@@ -774,6 +774,24 @@ class HipOps:
         self._chk(self.lib.tasu_f32_ca_attn(_p(q), q.stride(0), _p(table), V, D, H, denom, _p(out), out.stride(0), R, _p(ws), ws.numel(),
                                             self._stream()), "tasu_f32_ca_attn")
 
+    def f32_ca_attn_lse(self, q, table, out, lse, R, H, ws=None):
+        """f32_ca_attn for the training step (tasu_f32_ca_attn_lse): the same ``out`` bits, and ``lse`` [R, H] for f32_ca_attn_bwd."""
+        V, D = table.shape
+        if ws is None:
+            ws = torch.empty(max(self.f32_ca_workspace_floats(R, V, D, H), 1), device=table.device, dtype=torch.float32)
+        self._chk(self.lib.tasu_f32_ca_attn_lse(_p(q), q.stride(0), _p(table), V, D, H, float(D // H) ** 0.5, _p(out), out.stride(0), _p(lse),
+                                                R, _p(ws), ws.numel(), self._stream()), "tasu_f32_ca_attn_lse")
+
+    def f32_ca_attn_bwd(self, q, table, out, dout, lse, dq, R, H, ws=None):
+        """dq of the cross-attention projector's attention (tasu_f32_ca_attn_bwd) from the forward's ``out`` / ``lse`` and ``dout``;
+        ``ws`` as for f32_ca_attn."""
+        V, D = table.shape
+        if ws is None:
+            ws = torch.empty(max(self.f32_ca_workspace_floats(R, V, D, H), 1), device=table.device, dtype=torch.float32)
+        self._chk(self.lib.tasu_f32_ca_attn_bwd(_p(q), q.stride(0), _p(table), V, D, H, float(D // H) ** 0.5, _p(out), out.stride(0), _p(dout),
+                                                dout.stride(0), _p(lse), _p(dq), dq.stride(0), R, _p(ws), ws.numel(), self._stream()),
+                  "tasu_f32_ca_attn_bwd")
+
     def f32_ca_workspace_floats(self, R, V, D, H):
         return int(self.lib.tasu_f32_ca_workspace_floats(R, V, D, H))
 
@@ -786,6 +804,15 @@ class HipOps:
 
     def f32_silu(self, x, out, dy=None):
         self._chk(self.lib.tasu_f32_silu(_p(x), _p(dy), _p(out), x.numel(), self._stream()), "tasu_f32_silu")
+
+    def f32_relu_bwd(self, y, dy, out):
+        """out = dy where y > 0 else 0 (y: the ReLU's output or its input); may run in place on dy."""
+        self._chk(self.lib.tasu_f32_relu_bwd(_p(y), _p(dy), _p(out), y.numel(), self._stream()), "tasu_f32_relu_bwd")
+
+    def f32_lora_dropout(self, x, out, M, Cn, p, rng, sid, accumulate=False):
+        """out[M, Cn] = [out +] x * keep / (1 - p), the mask of lora_dropout (stream ``sid`` at rng = {seed, step}) in fp32."""
+        self._chk(self.lib.tasu_f32_lora_dropout(_p(x), x.stride(0), _p(out), out.stride(0), M, Cn, float(p), _p(rng), sid, int(accumulate),
+                                                 self._stream()), "tasu_f32_lora_dropout")
 
     def f32_colsum(self, x, out, R, Cn):
         self._chk(self.lib.tasu_f32_colsum(_p(x), x.stride(0), _p(out), R, Cn, self._stream()), "tasu_f32_colsum")

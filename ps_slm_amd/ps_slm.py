@@ -215,11 +215,24 @@ def model_factory(train_config, model_config, **kwargs):
     fp32_mode = not train_config.get("use_fp16", False)
     raw = not train_config.get("ctc_posterior", True)
     use_peft = bool(train_config.get("use_peft", False))
-    # the training step in fp32 (ps_slm_amd/train_fp32.py) serves the linear-silu projector without adapters; generate() and the
-    # eval-mode forward in fp32 (ps_slm_amd/decode_fp32.py) serve every projector and LoRA on the CTC-posterior branch
+    # by default the training step in fp32 (ps_slm_amd/train_fp32.py) is selected for the linear-silu projector without adapters;
+    # generate() and the eval-mode forward in fp32 (ps_slm_amd/decode_fp32.py) serve every projector and LoRA on the CTC-posterior branch
     f32_train_served = projector == "linear-silu" and not use_peft
     f32_eval_served = f32_train_served or not raw
-    if fp32_mode:
+    # train_config.mixed_precision (aispeech_asr_config.py:90; default true) chooses the arithmetic of the recipes whose fp32 training
+    # step is newer than their bf16 one: with use_fp16 = false, mixed_precision = false means "no bf16 anywhere" -- the alternate
+    # projectors and the LoRA adapters train in fp32 as well, and a recipe without an fp32 step is refused here instead of training in bf16 behind a log line
+    no_bf16 = fp32_mode and not train_config.get("mixed_precision", True)
+    if no_bf16 and not f32_train_served:
+        what = f"{projector} projector" + (" with LoRA adapters" if use_peft else "") + (" on raw encoder features" if raw else "")
+        if raw:
+            raise NotImplementedError(f"use_fp16=false with mixed_precision=false asks for fp32 everywhere; the {what} has no fp32 path "
+                                      "(ctc_posterior=false: the raw-feature branch runs on the bf16 kernels)")
+        f32_train_served = True
+        logger.warning("train_config.use_fp16 and mixed_precision are false: the reference's fp32 arithmetic everywhere -- generate(), "
+                       "evaluation and the training step of the %s run on the fp32 kernels (correctness mode: the training step is "
+                       "~10x slower than with use_fp16=true)", what)
+    elif fp32_mode:
         # the reference computes in fp32 unless use_fp16 wraps the step in bf16 autocast (deepspeed_utils.py:160,205) and ALWAYS
         # decodes in fp32 (inference_batch.py:113-117).  use_fp16 = false therefore selects the fp32 kernels for generate(), the
         # eval-mode forward and -- where train_fp32.py serves the model -- the training step; use_fp16 = true selects bf16 autocast

@@ -13,11 +13,15 @@ Multitask/scripts/finetune_deespeed_sensevoice.sh:37 -- forward and backward out
 
 A correctness mode: ~10x slower than the bf16 step at Qwen2.5-1.5B (271 against 28 ms per 16 utterances: the fp32 matrix rate is 1/16 of bf16's; the step runs at 0.61 of it); pinned on the
 real reference's fp32 goldens (loss within 2e-5, projector gradients within 2e-4 relative L2: tests/test_gpu_model.py).  Decoder weights stay
-frozen (dgrad only), like the bf16 step; LoRA and the non-default projectors train on the bf16 path only.
+frozen (dgrad only), like the bf16 step.  Every projector the package serves trains here -- linear-silu, linear and cov1d-linear
+(ReLU backward by the kept outputs' mask, the conv as one GEMM over the k-frame rows) and cross-attention (dq over the whole
+embedding table: tasu_f32_ca_attn_bwd, then dW_q = dq^T post) -- and so does an adapted decoder (use_peft: LoraF32 below, the
+unmerged forward y = W x + s B (A drop(x)) and the adapters' gradients into the bucket's tail).
 """
 import torch
 
 from .decode_fp32 import _gemm_ws, prompt_pass_fp32
+from .lora import TARGETS
 from .model import HD, StepState, rup
 
 
@@ -38,14 +42,25 @@ def forward_train_fp32(model, st: StepState):
     then the Vp-wide logits with the CE gradient written over them; loss / accuracy in ``st.dev['loss_out']`` like the bf16 step;
     ``st.fp32 = True`` routes ``TasuModel.run_backward`` to ``backward_fp32``."""
     ops, geo, llm, pr = model.ops, model.geo, model.llm, model.proj
-    if pr.kind != "linear-silu":
-        raise NotImplementedError(f"the fp32 training step serves the shipped projector (linear-silu), not {pr.kind!r}")
-    if model.lora is not None:                 # (the shared layers read the merged W + s B A; the backward's transposes are the base's)
-        raise NotImplementedError("the fp32 training step serves the frozen decoder without LoRA: an adapted model trains on the bf16 path")
+    # The shipped recipe (linear-silu, no adapters) trains in fp32 whenever use_fp16 = false.  The other recipes are opt-in: their
+    # default selection pins the bf16 step (model_factory: train_config.mixed_precision), so a model that was not selected for the
+    # fp32 step (arith_train != "fp32") is refused here, before any fp32 launch, instead of silently changing arithmetic
+    if model.arith_train != "fp32":
+        if model.lora is not None:
+            raise NotImplementedError("the fp32 training step of a LoRA model is opt-in: select it with train_config.use_fp16=false and "
+                                      "mixed_precision=false (arith_train = 'fp32'); by default an adapted model trains on the bf16 path")
+        if pr.kind != "linear-silu":
+            raise NotImplementedError(f"the fp32 training step serves the shipped projector (linear-silu) by default; for {pr.kind!r} it "
+                                      "is opt-in: train_config.use_fp16=false and mixed_precision=false (arith_train = 'fp32')")
+    if pr.kind != "linear-silu" and model.raw_features:
+        raise NotImplementedError("the fp32 training step of the alternate projectors serves the CTC-posterior branch (ctc_posterior=true)")
     M, D, V = st.M, geo.llm_dim, geo.llm_vocab
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
     keep = {}
+    st.lora_drop = model.lora is not None and lora_f32(model).drop_on()
+    if st.lora_drop:
+        ops.rng_advance(model.lora.rng)        # new masks for this micro-step, as the bf16 step draws them (TasuModel.forward_llm)
     xn, _, _ = prompt_pass_fp32(model, st, keep=keep)
     # ---- loss head: logits for every position (pad columns zeroed once: the lm_head dgrad contracts over Vp), CE + its gradient
     logits = buf("f32t_logits", (M, rup(V, 64)), f32)
@@ -73,6 +88,9 @@ def backward_fp32(model, st: StepState, on_ready=None):
     xs, qkvs, aos, gus = a["xs"], a["qkvs"], a["aos"], a["gus"]
     wt = _transposed_weights(model)
     ws = _gemm_ws(model)
+    lo = lora_f32(model) if model.lora is not None else None
+    drop = bool(getattr(st, "lora_drop", False))
+    xnb, actb = (buf("f32t_lora_xn", (M, D), f32), buf("f32t_lora_act", (M, I), f32)) if lo is not None else (None, None)
     dx, dn = buf("f32t_dx", (M, D), f32), buf("f32t_dn", (M, D), f32)
     dact, dgu = buf("f32t_dact", (M, I), f32), buf("f32t_dgu", (M, 2 * I), f32)
     dao, dqkv = buf("f32t_dao", (M, H * HD), f32), buf("f32t_dqkv", (M, LDQ), f32)
@@ -84,23 +102,225 @@ def backward_fp32(model, st: StepState, on_ready=None):
         w, t = llm.layers[l], wt["layers"][l]
         # MLP block: x_out = x_mid + down(swiglu(gate|up(norm(x_mid))))
         ops.f32_gemm(dx, t["wd"], dact, M, I, D, ws=ws)
+        if lo is not None and "down" in dict(lo.lp.groups):
+            ops.f32_swiglu(gus[l], actb, M, I)                                       # the down projection's input, rebuilt
+            lo.backward(l, "down", actb, dx, dact, M, ws, drop)
         ops.f32_swiglu_bwd(dact, gus[l], dgu, M, I)
         ops.f32_gemm(dgu, t["wgu"], dn, M, D, 2 * I, ws=ws)
+        if lo is not None and "gu" in dict(lo.lp.groups):
+            ops.f32_rmsnorm(xs[2 * l + 1], w["ln2"], xnb, M, D, geo.rms_eps)
+            lo.backward(l, "gu", xnb, dgu, dn, M, ws, drop)
         ops.f32_rmsnorm_bwd(dn, xs[2 * l + 1], w["ln2"], dx, M, D, geo.rms_eps, True)
         # attention block: x_mid = x_in + o(attention(rope(q|k|v(norm(x_in)))))
         ops.f32_gemm(dx, t["wo"], dao, M, H * HD, D, ws=ws)
+        if lo is not None:
+            lo.backward(l, "o", aos[l], dx, dao, M, ws, drop)
         ops.f32_attn_bwd(qkvs[l], dao, a["kstart"], dqkv, lse, delta, B, S, H, G, scale)
         ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
         ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, LDQ, ws=ws)
+        if lo is not None and "qkv" in dict(lo.lp.groups):
+            ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
+            lo.backward(l, "qkv", xnb, dqkv, dn, M, ws, drop)
         ops.f32_rmsnorm_bwd(dn, xs[2 * l], w["ln1"], dx, M, D, geo.rms_eps, True)
     d["dx"] = dx
-    if model.freeze_projector:
+    if model.freeze_projector:                 # (use_peft with a frozen projector: the adapters' tail of the bucket alone)
+        if on_ready is not None:
+            on_ready(model.lora.base, pr.numel)
         return
-    # ---- merge backward + projector backward (projector.py:149-151 reversed); weight gradients land in the flat bucket
-    Fap, Rap, K, Kp, Hb, Do = st.Fap, st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
+    # ---- merge backward + projector backward (projector.py:149-151 / :38-49 / :60-73 / :111-126 reversed); weight gradients land
+    # in the flat bucket
+    Rap, Kp, Do = st.Rap, pr.Kp, pr.Do
     rows = d["audio_rows_pad"] if "audio_rows_pad" in d else model._pad_rows(st)
     dy2 = buf("f32t_dy2", (Rap, Do), f32)
     ops.f32_gather_rows(dx, rows, dy2, Rap, Do)
+
+    def wgrad(dy, x, name, N, K, tag):
+        """g[name] [N, K] = dy^T x over the Rap rows (tasu_f32_gemm_nt contracts rows: both operands transposed)."""
+        dy_t, x_t = buf(f"f32t_{tag}_dy_t", (N, Rap), f32), buf(f"f32t_{tag}_x_t", (K, Rap), f32)
+        ops.f32_transpose(dy, dy_t, Rap, N, Rap)
+        ops.f32_transpose(x, x_t, Rap, K, Rap)
+        ops.f32_gemm(dy_t, x_t, pr.view(pr.g, name), N, K, Rap, ws=ws)
+
+    def dgrad(dy, name, N, K, tag):
+        """dy [Rap, N] W[name] [N, K] -> [Rap, K]."""
+        w_t, out = buf(f"f32t_{tag}_w_t", (K, N), f32), buf(f"f32t_{tag}_dx", (Rap, K), f32)
+        ops.f32_transpose(pr.view(pr.p, name), w_t, N, K, N)
+        ops.f32_gemm(dy, w_t, out, Rap, K, N, ws=ws)
+        return out
+
+    if pr.is_ca:
+        # dq of softmax(q E^T / sqrt(dh)) E over the whole embedding table, then dW_q = dq^T post
+        dq = buf("f32t_ca_dq", (Rap, Do), f32)
+        ops.f32_ca_attn_bwd(a["q"], llm.embed, a["out"], dy2, a["lse"], dq, Rap, geo.ca_heads, ws=a["ca_ws"])
+        wgrad(dq, d["post"], "W_q.weight", Do, Kp, "wq")
+    elif pr.has_norm:
+        _projector_backward_linear_silu(model, st, dy2, ws)
+    else:
+        # linear: [k frames] -> Linear -> ReLU -> Linear;  cov1d-linear: Conv1d over the k-frame rows -> ReLU -> the same
+        Hb, K1 = pr.Hb, pr.kin * Kp
+        ops.f32_colsum(dy2, pr.view(pr.g, pr.n_b2), Rap, Do)
+        wgrad(dy2, a["h"], pr.n_w2, Do, Hb, "w2")
+        dh = dgrad(dy2, pr.n_w2, Do, Hb, "w2")
+        ops.f32_relu_bwd(a["h"], dh, dh)
+        ops.f32_colsum(dh, pr.view(pr.g, pr.n_b1), Rap, Hb)
+        wgrad(dh, a["x1"], pr.n_w1, Hb, K1, "w1")
+        if pr.has_conv:
+            dc0 = dgrad(dh, pr.n_w1, Hb, Kp, "w1")
+            ops.f32_relu_bwd(a["x1"], dc0, dc0)
+            ops.f32_colsum(dc0, pr.view(pr.g, "conv1d.bias"), Rap, Kp)
+            wgrad(dc0, a["xcat"], "conv1d.weight", Kp, pr.k * Kp, "w0")
+    if on_ready is not None:
+        on_ready(0, pr.numel)
+
+
+# ------------------------------------------------------------------------------------------------ LoRA (use_peft = true) in fp32
+class LoraF32:
+    """The adapters of an adapted decoder in the fp32 training step.  In training mode peft's lora.Linear runs UNMERGED,
+    y = W x + s B (A drop(x)) (a dropout mask cannot be merged into W), so the step's forward runs every adapted Linear on the base
+    fp32 weights and adds the low-rank branch; eval mode and generate() keep the merged W + s B A (lora.merged_llm_f32).
+
+    forward, per adapted Linear t of a group:   us_t = drop(x) (s A_t)^T  [M, r]   (kept per layer: 4 r bytes per row and target)
+                                                y[:, cols of t] += us_t B_t^T
+    backward, from the group's output gradient: v = dy_t (s B_t)  [M, r];   dx += mask . (v A_t);   dB_t = dy_t^T us_t;   dA_t = v^T drop(x)
+    The adapter inputs are not stored: drop(x) is rebuilt in the backward from what the step keeps anyway (the residual stream ->
+    RMSNorm, the attention output, gate|up -> SwiGLU) and the counter-based mask of the forward (tasu_f32_lora_dropout: the masks of
+    the bf16 step, regenerated from {seed, step, stream id, element index}) -- the same bits as the forward's, no [L, M, in] copies.
+    Every thin product ([M, r], r = 8..64) is tasu_f32_gemm_nt: it serves any M and N, its K granule is 32, so operands whose
+    contraction runs over the rank are zero-padded to rk = 32-multiples (working copies below) and the accumulate y += us B^T is
+    its ``resid`` aliasing C; the weight gradients contract the M rows (both operands transposed, rows zero-padded to 32)."""
+
+    def __init__(self, model):
+        self.m, self.lp = model, model.lora
+        self.rk = rup(self.lp.r, 32)
+        self.version = -1
+        self.w = {}
+
+    def weights(self):
+        """fp32 working copies from the master adapters, rebuilt when they changed (lp.version: a load, an optimizer step):
+        sA [r, in], Bp [out, rk] (rank columns zero-padded), sBt [r, out] = s B^T, At [in, rk] = A^T zero-padded."""
+        lp = self.lp
+        if self.version == lp.version:
+            return self.w
+        p, s, r, rk = lp.proj.p, float(lp.cfg.scaling), lp.r, self.rk
+        for l in range(self.m.geo.llm_layers):
+            for t in lp.cfg.target_modules:
+                (i, o), A, B = lp.dims[t], lp.view(p, l, t, "A"), lp.view(p, l, t, "B")
+                w = self.w.get((l, t))
+                if w is None:
+                    z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=p.device)
+                    w = self.w[(l, t)] = dict(sA=z(r, i), Bp=z(o, rk), sBt=z(r, o), At=z(i, rk))
+                w["sA"].copy_(A).mul_(s)
+                w["Bp"][:, :r].copy_(B)
+                w["sBt"].copy_(B.t()).mul_(s)
+                w["At"][:, :r].copy_(A.t())
+        self.version = lp.version
+        return self.w
+
+    def drop_on(self):
+        return bool(self.m.training and self.lp.cfg.lora_dropout > 0.0)
+
+    def _sid(self, l, t):
+        return l * 8 + TARGETS.index(t)
+
+    def _us(self, t, M):
+        """[L, M, rk] rank activations of target t, kept for the backward; the pad columns [r, rk) are zero."""
+        m, name = self.m, "f32t_lora_us_" + t
+        before = m._ws.get(name)
+        buf = m._buf(name, (m.geo.llm_layers, M, self.rk), torch.float32)
+        if before is not m._ws[name]:
+            m._ws[name].zero_()
+        return buf
+
+    def _dropped(self, l, t, x, M, width, drop):
+        if not drop:
+            return x
+        xd = self.m._buf("f32t_lora_xd", (M, width), torch.float32)
+        self.m.ops.f32_lora_dropout(x, xd, M, width, self.lp.cfg.lora_dropout, self.lp.rng, self._sid(l, t))
+        return xd
+
+    def forward(self, l, gname, x, y, M, ws, drop):
+        """y [M, nout of the group] (the base Linear's output, bias / residual included) += every member's low-rank branch."""
+        lp, ops, W = self.lp, self.m.ops, self.weights()
+        for t in dict(lp.groups).get(gname, ()):
+            (i, o), c0, w = lp.dims[t], lp.cols[t], W[(l, t)]
+            us = self._us(t, M)[l]
+            ops.f32_gemm(self._dropped(l, t, x, M, i, drop), w["sA"], us, M, lp.r, i, ws=ws)
+            ops.f32_gemm(us, w["Bp"], y[:, c0:c0 + o], M, o, self.rk, resid=y[:, c0:c0 + o], ws=ws)
+
+    def backward(self, l, gname, x, dy, dx_base, M, ws, drop):
+        """dy [M, nout of the group]; x: the group's (undropped) input [M, in]; dx_base [M, in] += every member's input gradient;
+        dA / dB of the members into the adapter tail of the bucket."""
+        lp, m, ops, W = self.lp, self.m, self.m.ops, self.weights()
+        targets = dict(lp.groups).get(gname, ())
+        if not targets:
+            return
+        f32, r, rk, Mp = torch.float32, lp.r, self.rk, rup(M, 32)
+        p, g = lp.cfg.lora_dropout, lp.proj.g
+        inn, width = lp.dims[targets[0]][0], dy.shape[1]
+        dy_t = m._buf("f32t_lora_dy_t", (width, Mp), f32)
+        ops.f32_transpose(dy, dy_t, M, width, Mp)
+        v = m._buf("f32t_lora_v", (M, rk), f32)
+        if rk != r:
+            v[:, r:].zero_()
+        x_t, last = m._buf("f32t_lora_x_t", (inn, Mp), f32), None
+        r_t = m._buf("f32t_lora_r_t", (rk, Mp), f32)
+        for t in targets:
+            (i, o), c0, w = lp.dims[t], lp.cols[t], W[(l, t)]
+            ops.f32_gemm(dy[:, c0:c0 + o], w["sBt"], v, M, r, o, ws=ws)                        # v = dy_t (s B)
+            if drop:                                                                           # dx += mask . (v A)
+                tmp = m._buf("f32t_lora_tmp", (M, i), f32)
+                ops.f32_gemm(v, w["At"], tmp, M, i, rk, ws=ws)
+                ops.f32_lora_dropout(tmp, dx_base, M, i, p, lp.rng, self._sid(l, t), accumulate=True)
+            else:
+                ops.f32_gemm(v, w["At"], dx_base, M, i, rk, resid=dx_base, ws=ws)
+            ops.f32_transpose(self._us(t, M)[l], r_t, M, rk, Mp)
+            ops.f32_gemm(dy_t[c0:c0 + o], r_t, lp.view(g, l, t, "B"), o, r, Mp, ws=ws)         # dB = dy_t^T us
+            xd = self._dropped(l, t, x, M, i, drop)
+            if drop or last is None:                                                           # members share x unless dropout gave each its own
+                ops.f32_transpose(xd, x_t, M, i, Mp)
+                last = xd
+            ops.f32_transpose(v, r_t, M, rk, Mp)
+            ops.f32_gemm(r_t, x_t, lp.view(g, l, t, "A"), r, i, Mp, ws=ws)                     # dA = v^T drop(x)
+
+
+def lora_f32(model):
+    run = getattr(model, "_lora_f32", None)
+    if run is None or run.lp is not model.lora:
+        run = model._lora_f32 = LoraF32(model)
+    return run
+
+
+def lora_layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, keep_gu=True):
+    """decode_fp32._layer_fp32 for the training step of an adapted decoder: the same layer on the BASE fp32 weights with every
+    adapted Linear's low-rank branch added before the operator behind it (RoPE, the residual's RMSNorm, SwiGLU), unfused."""
+    ops, geo, llm = model.ops, model.geo, model.llm
+    D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
+    f, w = llm.f32["layers"][l], llm.layers[l]
+    lo = lora_f32(model)
+    drop = lo.drop_on()
+    LDQ = (H + 2 * G) * HD
+    ops.f32_gemm(xn, f["wqkv"], qkv, rows, LDQ, D, bias=f["bqkv"], ws=ws)
+    lo.forward(l, "qkv", xn, qkv, rows, ws, drop)
+    ops.f32_rope(qkv, cos_t, sin_t, rows, H, G)
+    attend(l, qkv, ao)
+    ops.f32_gemm(ao, f["wo"], x_mid, rows, D, H * HD, resid=x_in, ws=ws)
+    lo.forward(l, "o", ao, x_mid, rows, ws, drop)
+    ops.f32_rmsnorm(x_mid, w["ln2"], xn, rows, D, geo.rms_eps)
+    ops.f32_gemm(xn, f["wgu"], gu, rows, 2 * I, D, ws=ws)
+    lo.forward(l, "gu", xn, gu, rows, ws, drop)
+    ops.f32_swiglu(gu, act, rows, I)
+    ops.f32_gemm(act, f["wd"], x_out, rows, D, I, resid=x_mid, ws=ws)
+    lo.forward(l, "down", act, x_out, rows, ws, drop)
+    ops.f32_rmsnorm(x_out, llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm, xn, rows, D, geo.rms_eps)
+
+
+def _projector_backward_linear_silu(model, st, dy2, ws):
+    """LayerNorm -> Linear -> SiLU -> Linear (the shipped projector) from the output rows' gradient dy2."""
+    ops, pr = model.ops, model.proj
+    f32 = torch.float32
+    buf, d = model._buf, st.dev
+    a = d["f32t"]
+    Rap, K, Kp, Hb, Do = st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
     ops.f32_colsum(dy2, pr.view(pr.g, pr.n_b2), Rap, Do)
     dy2_t, h_t = buf("f32t_dy2_t", (Do, Rap), f32), buf("f32t_h_t", (Hb, Rap), f32)
     ops.f32_transpose(dy2, dy2_t, Rap, Do, Rap)
@@ -121,5 +341,3 @@ def backward_fp32(model, st: StepState, on_ready=None):
     dxn = buf("f32t_dxn", (Rap, Kp), f32)
     ops.f32_gemm(dh, w1_t, dxn, Rap, Kp, Hb, ws=ws)
     ops.f32_layernorm_bwd_params(dxn, d["post"], a["mean"], a["rstd"], pr.view(pr.g, "norm.weight"), pr.view(pr.g, "norm.bias"), Rap, K)
-    if on_ready is not None:
-        on_ready(0, pr.numel)

@@ -1,6 +1,7 @@
 """fp32 cross-attention projector kernel (tasu_f32_ca_attn) and fp32 generate() of a LoRA model against its base model.
 
     python tools/bench_f32_ca.py
+    python tools/bench_f32_ca.py --bwd       # the kernel legs only, forward and backward (tasu_f32_ca_attn_bwd: 6 R V D FLOP)
 
 Kernel: the Qwen2.5-1.5B (D = 1536, dh = 192) and 7B (D = 3584, dh = 448) geometries, V = 151,936, R in {64, 512}; reported in ms
 and as the fraction of the 157 TFLOPS fp32 matrix peak (4 R V D FLOP: two products of R x V x dh per head).  Decode: fp32
@@ -36,6 +37,29 @@ def time_ca(ops, R, D, V=151936, H=8, reps=10):
     ms = ev[0].elapsed_time(ev[1]) / reps
     flop = 4.0 * R * V * D
     return {"kernel": "tasu_f32_ca_attn", "R": R, "V": V, "D": D, "dh": D // H, "ms": round(ms, 3),
+            "tflops": round(flop / ms / 1e9, 1), "frac_f32_peak": round(flop / (ms * 1e-3) / PEAK_F32, 3)}
+
+
+def time_ca_bwd(ops, R, D, V=151936, H=8, reps=10):
+    """tasu_f32_ca_attn_bwd: three products of R x V x dh per head (S = Q K^T, dP = dO K^T, dq = dS K)."""
+    g = torch.Generator(device="cuda").manual_seed(R + D)
+    table = torch.randn(V, D, generator=g, device="cuda") * 0.02
+    q, dout = torch.randn(R, D, generator=g, device="cuda"), torch.randn(R, D, generator=g, device="cuda")
+    out, lse, dq = torch.empty(R, D, device="cuda"), torch.empty(R, H, device="cuda"), torch.empty(R, D, device="cuda")
+    ws = torch.empty(ops.f32_ca_workspace_floats(R, V, D, H), device="cuda")
+    ops.f32_ca_attn_lse(q, table, out, lse, R, H, ws=ws)
+    for _ in range(2):
+        ops.f32_ca_attn_bwd(q, table, out, dout, lse, dq, R, H, ws=ws)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        ops.f32_ca_attn_bwd(q, table, out, dout, lse, dq, R, H, ws=ws)
+    ev[1].record()
+    torch.cuda.synchronize()
+    ms = ev[0].elapsed_time(ev[1]) / reps
+    flop = 6.0 * R * V * D
+    return {"kernel": "tasu_f32_ca_attn_bwd", "R": R, "V": V, "D": D, "dh": D // H, "ms": round(ms, 3),
             "tflops": round(flop / ms / 1e9, 1), "frac_f32_peak": round(flop / (ms * 1e-3) / PEAK_F32, 3)}
 
 
@@ -79,9 +103,14 @@ def time_generate(use_peft, B=16, new_tokens=64, beams=4):
 def main():
     from ps_slm_amd.ops import HipOps
     ops = HipOps()
+    bwd = "--bwd" in sys.argv[1:]
     for D in (1536, 3584):
         for R in (64, 512):
             print(json.dumps(time_ca(ops, R, D)), flush=True)
+            if bwd:
+                print(json.dumps(time_ca_bwd(ops, R, D)), flush=True)
+    if bwd:
+        return
     torch.cuda.empty_cache()
     for use_peft in (False, True):
         print(json.dumps(time_generate(use_peft)), flush=True)

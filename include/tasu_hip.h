@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 18
+#define TASU_ABI_VERSION 19
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -479,6 +479,15 @@ int tasu_embed_merge_fwd(const float* table, const void* proj_bf16, const int32_
                          float* x, int M, int D, void* stream);
 /* dproj[r,:] = bf16(dx[audio_rows[r],:]) for r < n_audio (gather of the gradient rows that hold audio).   */
 int tasu_merge_bwd(const float* dx, const int32_t* audio_rows, void* dproj_bf16, int n_audio, int D, void* stream);
+/* Lookup term of the embedding table's gradient (train_config.use_emb, ps-slm.py:119-123, :525): dtable[id, :] += the sum of the
+ * rows of dx [n_dx, D] that looked row id up.  The host orders the text rows by token id: rows [n_rows] holds row numbers of dx
+ * (an entry < 0 or >= n_dx contributes nothing), segment s is rows[seg_start[s] .. seg_start[s + 1]) (seg_start has n_seg + 1
+ * entries) and belongs to table row seg_id[s]; a segment whose id is < 0 or >= V is skipped, so a list padded with such entries
+ * keeps one launch shape.  The ids of the segments that are not skipped must be DISTINCT (the host's plan lists every id once):
+ * each segment is summed by one wave in the order of the list and added ONCE to its row with plain vector stores -- no atomics,
+ * the same bits on every run.  Rows no segment names are not touched.  D % 4 == 0, 16-byte aligned dx / dtable.             */
+int tasu_embed_bwd(const float* dx, const int32_t* rows, const int32_t* seg_start, const int32_t* seg_id, float* dtable,
+                   int n_dx, int n_rows, int n_seg, int V, int D, void* stream);
 
 /* --------------------------------------------------------------------------------------------- AdamW
  * DeepSpeed FusedAdam(adam_w_mode) of Multitask/conf/ds_config.json:4-11 over one flat fp32 buffer:

@@ -69,6 +69,7 @@ PROTOTYPES = {
     "tasu_posterior_build": [vp, vp, vp, i32, i32, i32, vp],
     "tasu_embed_merge_fwd": [vp, vp, vp, vp, vp, i32, i32, vp],
     "tasu_merge_bwd": [vp, vp, vp, i32, i32, vp],
+    "tasu_embed_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "tasu_adamw": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp],
     "tasu_sinusoid_pe": [vp, vp, i32, i32, i32, f32, vp],
     "tasu_fsmn_fwd": [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -167,7 +168,7 @@ PROTOTYPES.update({
     "tasu_f32_attn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
 })
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

@@ -52,6 +52,32 @@ __global__ __launch_bounds__(256) void merge_bwd_kernel(const float* __restrict_
   }
 }
 
+// dtable[seg_id[s], :] += sum over j in [seg_start[s], seg_start[s + 1]) of dx[rows[j], :], one wave per segment, rows in list order
+// (fixed summation order, one plain read-modify-write of the destination row: the segments' ids are distinct).  Everything read
+// from the device-side plan is range-checked before it becomes an address.
+__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ dx, const int32_t* __restrict__ rows,
+                                                        const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_id,
+                                                        float* __restrict__ dtable, int n_dx, int n_rows, int n_seg, int V, int D) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (s >= n_seg) return;
+  const int id = seg_id[s];
+  if (id < 0 || id >= V) return;
+  int j0 = seg_start[s], j1 = seg_start[s + 1];
+  j0 = j0 < 0 ? 0 : j0;
+  j1 = j1 > n_rows ? n_rows : j1;
+  if (j0 >= j1) return;
+  float* o = dtable + (size_t)id * D;
+  for (int c = lane * 4; c < D; c += 256) {
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = j0; j < j1; ++j) {
+      const int m = rows[j];
+      if (m >= 0 && m < n_dx) acc += *(const f32x4*)(dx + (size_t)m * D + c);
+    }
+    *(f32x4*)(o + c) = *(const f32x4*)(o + c) + acc;
+  }
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16* __restrict__ pb, int64_t n,
                                                     float lr, float b1, float b2, float eps, float wd,
@@ -100,6 +126,16 @@ extern "C" int tasu_merge_bwd(const float* dx, const int32_t* audio_rows, void* 
   if (!dx || !audio_rows || !dproj || n_audio <= 0 || D <= 0 || D % 4) return TASU_ERR_ARG;
   TASU_LAUNCH(merge_bwd_kernel, dim3((n_audio + 3) / 4), dim3(256), 0, (hipStream_t)stream, dx, audio_rows,
                      (bf16*)dproj, n_audio, D);
+  return TASU_OK;
+}
+
+extern "C" int tasu_embed_bwd(const float* dx, const int32_t* rows, const int32_t* seg_start, const int32_t* seg_id, float* dtable,
+                              int n_dx, int n_rows, int n_seg, int V, int D, void* stream) {
+  if (!dx || !rows || !seg_start || !seg_id || !dtable || n_dx <= 0 || n_rows <= 0 || n_seg <= 0 || V <= 0 || D <= 0 || D % 4)
+    return TASU_ERR_ARG;
+  if (((uintptr_t)dx & 15) || ((uintptr_t)dtable & 15)) return TASU_ERR_ARG;
+  TASU_LAUNCH(embed_bwd_kernel, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, dx, rows, seg_start, seg_id, dtable, n_dx,
+              n_rows, n_seg, V, D);
   return TASU_OK;
 }
 

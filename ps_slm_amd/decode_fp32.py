@@ -44,7 +44,7 @@ def _fragments(model):
         return None
     f32 = weights_f32(model)
     fr = f32.get("frag")
-    if fr is None:
+    if fr is None or fr.get("head") is None:               # (head None: the tied embedding table changed, the layers' copies stand)
         ops, nws = model.ops, _gemm_ws(model).numel()
 
         def to(w):                                         # only what the streaming kernel will read (Qwen2.5-7B's down projection,
@@ -52,10 +52,12 @@ def _fragments(model):
             return ops.f32_to_fragments(w) if ops.lib.tasu_f32_gemm_streams(64, N, K, nws) == 1 else w
         # a merged LoRA set shares the base lm_head: its fragment copy is the base set's, or the one kept across adapter updates
         base_fr = model.llm.f32.get("frag") if f32 is not model.llm.f32 else None
-        head = base_fr["head"] if base_fr is not None else f32.get("frag_head")
+        head = base_fr["head"] if base_fr is not None and base_fr.get("head") is not None else f32.get("frag_head")
         if head is None:
             head = f32["frag_head"] = to(f32["head"])
-        fr = f32["frag"] = dict(layers=[dict(wgu=to(f["wgu"]), wd=to(f["wd"])) for f in f32["layers"]], head=head)
+        if fr is None:
+            fr = f32["frag"] = dict(layers=[dict(wgu=to(f["wgu"]), wd=to(f["wd"])) for f in f32["layers"]])
+        fr["head"] = head
     return fr
 
 

@@ -468,6 +468,10 @@ class TasuModel:
         self._dec_graphs = GraphCache(8)
         self._done_host = None         # pinned "decode finished" word the beam-update kernel writes
         self.lora = None               # ps_slm_amd.lora.LoraParams once enable_lora() ran (use_peft=true)
+        # train_config.use_emb (enable_embedding_training): where the decoder's embedding table starts in the trainable bucket, or None;
+        # embed_version counts changes of the table's values (optimizer step, load) for everything that caches a copy of it
+        self.embed_base = None
+        self.embed_version = 0
         self.freeze_projector = False  # train_config.freeze_projector (ps-slm.py:50-54): the projector's weight gradients, exchange and
                                        # optimizer update are skipped; only the adapters train (the plugin refuses it without use_peft)
         self.raw_features = geo.proj_in not in (0, geo.ctc_vocab)   # ctc_posterior=false: the projector reads encoder states
@@ -485,6 +489,8 @@ class TasuModel:
         self.llm.load_reference_state_dict(sd)
         if self.lora is not None:
             self.lora.build_ext(self.llm)                  # [W | B] copies of the adapted Linears follow the new base weights
+        if self.embed_base is not None:
+            self._adopt_embed()                            # the new table moves into the bucket
         for n in self.proj.names:
             self.proj.load(n, sd["encoder_projector." + n].to(self.device, torch.float32))
         self.sync_projector_copies()
@@ -506,6 +512,8 @@ class TasuModel:
         self.llm.init_random(seed)
         if self.lora is not None:
             self.lora.build_ext(self.llm)
+        if self.embed_base is not None:
+            self._adopt_embed()
         self.init_projector_default(seed + 1)
         if with_encoder:
             from .encoder import EncoderWeights
@@ -561,6 +569,113 @@ class TasuModel:
         self.proj.refresh_working_copies(self.ops)
         if self.lora is not None:
             self.lora.refresh_working_copies(self.ops)
+        if self.embed_base is not None:
+            self._embed_changed()
+
+    # ---- train_config.use_emb: the decoder's input embedding table as a trainable tensor (ps-slm.py:119-123)
+    def enable_embedding_training(self):
+        """use_peft=true with use_emb=true: the table [V, D] joins the trainable bucket behind the adapters,
+        [projector | adapters | embedding table], start aligned to 64 elements.  From here on ``llm.embed`` (the fp32 master) is a
+        view of ``proj.p`` and, with tied embeddings, ``llm.head`` (the bf16 lm_head) a view of ``proj.pb`` -- the bf16 image the
+        AdamW kernel writes -- so that one optimizer launch moves the table and the head together.  An untied head stays frozen.
+        Call after enable_lora and before an engine is built on the model (the bucket grows)."""
+        if self.embed_base is not None:
+            raise RuntimeError("the embedding table is already trainable on this model")
+        if self.arith_train == "fp32":
+            raise NotImplementedError("use_emb on the fp32 training step: ps_slm_amd/train_fp32.py has no backward into the embedding "
+                                      "table (the table trains on the bf16-autocast step)")
+        pr, geo = self.proj, self.geo
+        if geo.llm_dim % 4:
+            raise NotImplementedError(f"use_emb: llm_dim {geo.llm_dim} is not a multiple of 4 (16-byte rows of the table's gradient)")
+        self._embed_tail_lo, base = pr.numel, rup(pr.numel, 64)
+        pr.extend(base - pr.numel + geo.llm_vocab * geo.llm_dim)
+        self.embed_base = base
+        self._adopt_embed()
+
+    @property
+    def proj_end(self):
+        """Where the projector's own tensors end in the bucket (the adapters, else the embedding table, else nothing follows)."""
+        if self.lora is not None:
+            return self.lora.base
+        return self.proj.numel if self.embed_base is None else self._embed_tail_lo
+
+    @property
+    def embed_range(self):
+        """[lo, hi) of the embedding table in the flat trainable bucket."""
+        return self.embed_base, self.embed_base + self.geo.llm_vocab * self.geo.llm_dim
+
+    def embed_view(self, flat):
+        lo, hi = self.embed_range
+        return flat[lo:hi].view(self.geo.llm_vocab, self.geo.llm_dim)
+
+    def embed_grad(self):
+        return self.embed_view(self.proj.g).detach().clone()
+
+    def _adopt_embed(self):
+        """Moves the table the LLM weights hold into its range of the bucket and re-points the views (at enable time, and after the
+        LLM was reloaded or the bucket re-allocated); every captured graph refers to the old tensors and is dropped."""
+        llm, pr = self.llm, self.proj
+        tab = self.embed_view(pr.p)
+        if llm.embed.data_ptr() != tab.data_ptr():
+            tab.copy_(llm.embed)
+        llm.embed = tab
+        if self.geo.tied:
+            new = self.embed_view(pr.pb)
+            if llm.head is not None and llm.head.data_ptr() != new.data_ptr():
+                llm._stale_ptrs.append(llm.head.data_ptr())        # its fragment-order decode copy dies with it
+            llm.head = new
+            if llm.f32 is not None:
+                llm.f32["head"] = llm.embed                         # tied: one fp32 copy, the master itself
+        llm._ca_e = llm._ca_et = None                               # (untied cross-attention tables: rebuilt on first use)
+        llm._decode_ready = False
+        if self.lora is not None:
+            self.lora._merged32 = None                              # (holds the fp32 head by reference)
+            merged = self.lora._merged                              # the bf16 merged set shares embed / head / head_t by reference
+            if merged is not None:
+                merged.embed, merged.head, merged.head_t, merged._decode_ready = llm.embed, llm.head, llm.head_t, False
+        self._graphs.clear()
+        self._dec_graphs.clear()
+        self.sync_projector_copies()
+
+    def load_embed(self, t):
+        """New values for the embedding table (a checkpoint written with use_emb): into the master in place -- the bucket's range
+        when the table is trainable, the frozen tensor otherwise (the table is a value of the decoder: inference needs it either
+        way).  The caller runs sync_projector_copies() afterwards."""
+        self.llm.embed.copy_(t.to(self.device, torch.float32))
+        if self.embed_base is None:
+            self._embed_changed()
+
+    def _embed_changed(self):
+        """The table's values changed (optimizer step, load): everything that caches a copy follows.  Tied: the [D, Vpad] transpose of
+        the head for the lm_head dgrad (one transpose of the bf16 image), the fragment-order decode copy of the head (dropped and
+        registered again at the next generate(); the decode graphs hold its address), the fp32 decode path's fragment-order head.
+        Untied: the cross-attention projector's bf16 tables.  bf16 prefill, the fp32 eval forward and the training step read
+        ``llm.embed`` / ``llm.head`` themselves, which ARE the bucket."""
+        llm, geo, ops = self.llm, self.geo, self.ops
+        self.embed_version += 1
+        V, D, Vp = geo.llm_vocab, geo.llm_dim, rup(geo.llm_vocab, 64)
+        if geo.tied:
+            if self.embed_base is None:
+                ops.cast_bf16(llm.embed, llm.head)                  # frozen table, loaded values: the head's own bf16 tensor
+            ops.transpose(llm.head, llm.head_t, V, D, Vp, D)
+            if hasattr(ops, "forget_decode_weights"):
+                ops.forget_decode_weights([llm.head.data_ptr()])
+            llm._decode_ready = False
+            merged = getattr(self.lora, "_merged", None)
+            if merged is not None:
+                merged._decode_ready = False
+            self._dec_graphs.clear()
+            # fp32 paths: only the HEAD's fragment-order copy and transpose are stale; the layers' copies (gigabytes) stand
+            for f in (llm.f32, getattr(self.lora, "_merged32", None)):
+                if f:
+                    f.pop("frag_head", None)
+                    for k in ("frag", "t"):
+                        if f.get(k) is not None:
+                            f[k]["head"] = None
+        elif getattr(llm, "_ca_e", None) is not None:
+            if self.embed_base is None:
+                ops.cast_bf16(llm.embed, llm._ca_e)
+            ops.transpose(llm._ca_e, llm._ca_et, V, D, Vp, D)
 
     def enable_lora(self, cfg, seed=4242):
         """use_peft=true (ps-slm.py:114-117): adapters on the decoder's Linears, trainable next to the projector.  Call before
@@ -568,6 +683,8 @@ class TasuModel:
         from .lora import LoraParams, LoraRunner
         if self.lora is not None:
             raise RuntimeError("LoRA is already enabled on this model")
+        if self.embed_base is not None:
+            raise RuntimeError("enable_lora after enable_embedding_training: the bucket is laid out [projector | adapters | embedding table]")
         self.lora = LoraParams(self.geo, cfg, self.proj, self.device)
         self.lora.build_ext(self.llm)
         self.lora.init_default(seed)
@@ -796,7 +913,29 @@ class TasuModel:
             st.dev["lab_rows0"] = self._upload("lab_rows0", np.maximum(lab_rows, 0), flush=False)   # padding slots read row 0 (their results are ignored)
             st.dev["lab_compact"] = self._upload("lab_compact", lab_c, flush=False)
             st.dev["lab_slot"] = self._upload("lab_slot", slot, flush=False)
+            if self.embed_base is not None:
+                self._embed_plan(st, plan)
         return st
+
+    def _embed_plan(self, st, plan):
+        """use_emb: the rows that looked the embedding table up (kind 1), ordered by token id, as segments of equal id for
+        tasu_embed_bwd.  All three arrays have lengths that depend on M alone (rows and segment ids padded with -1, segment starts
+        with the number of text rows), so the launch shape is fixed by what _shape_key holds and a graph replay reads the plan of
+        ITS batch out of the fixed upload slots."""
+        M = st.M
+        kind, idx = np.asarray(plan.src_kind).reshape(-1), np.asarray(plan.src_idx).reshape(-1)
+        text = np.nonzero(kind == 1)[0]
+        order = np.argsort(idx[text], kind="stable")
+        ids, first = np.unique(idx[text][order], return_index=True)
+        rows = np.full(M, -1, dtype=np.int32)
+        rows[: len(text)] = text[order]
+        seg_id = np.full(M, -1, dtype=np.int32)
+        seg_id[: len(ids)] = ids
+        seg_start = np.full(M + 1, len(text), dtype=np.int32)
+        seg_start[: len(ids)] = first
+        st.dev["emb_rows"] = self._upload("emb_rows", rows, flush=False)
+        st.dev["emb_seg_start"] = self._upload("emb_seg_start", seg_start, flush=False)
+        st.dev["emb_seg_id"] = self._upload("emb_seg_id", seg_id, flush=False)
 
     # ------------------------------------------------------------------------------------------ forward
     def forward_projector_text(self, st: StepState):
@@ -851,7 +990,8 @@ class TasuModel:
             return llm.head, llm.head_t
         if getattr(llm, "_ca_e", None) is None:
             V, D, Vp = geo.llm_vocab, geo.llm_dim, rup(geo.llm_vocab, 64)
-            e = llm.embed.to(torch.bfloat16).contiguous()
+            # a trained table (use_emb): its bf16 image in the bucket, which AdamW writes; _embed_changed() redoes the transpose
+            e = self.embed_view(self.proj.pb) if self.embed_base is not None else llm.embed.to(torch.bfloat16).contiguous()
             et = torch.zeros(D, Vp, dtype=torch.bfloat16, device=self.device)
             et[:, :V].copy_(e.t())
             llm._ca_e, llm._ca_et = e, et
@@ -912,7 +1052,7 @@ class TasuModel:
         ops.transpose(d["xn"].view(Rap, Kp), xn_t, Rap, Kp, Rap, Kp)
         ops.gemm(dq_t, xn_t, pr.view(pr.g, "W_q.weight"), D, Kp, Rap, mode=GEMM_F32)
         if on_ready is not None:
-            on_ready(0, pr.numel if self.lora is None else self.lora.base)
+            on_ready(0, self.proj_end)
 
     def forward_llm(self, st: StepState, compute_loss=True, need_backward=True, logits_rows="all"):
         ops, geo, llm = self.ops, self.geo, self.llm
@@ -978,7 +1118,7 @@ class TasuModel:
         ops.rmsnorm_fwd(xs[2 * L], llm.norm, xn, rstd[2 * L], geo.rms_eps)
         logits = self._buf("logits", (M, Vp), bf)
         ops.gemm(xn, llm.head, logits, M, V, D)
-        d.update(logits=logits)
+        d.update(logits=logits, xn_head=xn)
         if not compute_loss:
             return
         row_loss = self._buf("row_loss", (M,), f32)
@@ -1020,7 +1160,7 @@ class TasuModel:
         ops.ce_fwd_bwd(logits, d["lab_compact"], n, V, row_loss, row_hit, None, logits, d["inv_count"])   # dlogits in place
         res = self._buf("loss_out", (4,), f32)
         ops.ce_reduce(row_loss, row_hit, d["lab_compact"], n, res)
-        d.update(dlogits=logits, loss_out=res, row_arg=None, rstd_lab=rstd_c, labelled_only=True)
+        d.update(dlogits=logits, loss_out=res, row_arg=None, rstd_lab=rstd_c, labelled_only=True, xn_head=xn_c)
         d.pop("logits", None)
 
     # ------------------------------------------------------------------------------------------ backward
@@ -1029,6 +1169,42 @@ class TasuModel:
         self.backward_llm(st)
         if not self.freeze_projector:
             self.backward_projector(st, on_ready, w1_chunks)
+        if self.embed_base is not None:
+            self.backward_embed(st, on_ready)
+
+    def _head_wgrad(self, st):
+        """use_emb with tied embeddings: the lm_head's weight gradient dW = dlogits^T h is the second term of the table's gradient
+        (h: the final-normed rows that fed the lm_head GEMM -- the compact labelled rows in the throughput mode).  fp32, on the MFMA
+        GEMM behind the transposes the projector's dW1 uses, straight into (overwriting) the table's range of the bucket; rows
+        without a label and the padding rows have dlogits == 0 / h == 0."""
+        ops, geo, d = self.ops, self.geo, st.dev
+        V, D, Vp = geo.llm_vocab, geo.llm_dim, rup(geo.llm_vocab, 64)
+        n = st.nLp if d.get("labelled_only") else st.M
+        npad = rup(n, 64)
+        dl_t = self._buf("emb_dl_t", (Vp, npad), torch.bfloat16)
+        h_t = self._buf("emb_h_t", (D, npad), torch.bfloat16)
+        ops.transpose(d["dlogits"], dl_t, n, Vp, npad, Vp)
+        ops.transpose(d["xn_head"], h_t, n, D, npad, D)
+        ops.gemm(dl_t, h_t, self.embed_view(self.proj.g), V, D, npad, mode=GEMM_F32)
+
+    def backward_embed(self, st, on_ready=None):
+        """use_emb: the lookup term of the table's gradient -- every text row of dx = d(loss)/d(inputs_embeds) added into the row of
+        its token id (ps-slm.py:525; the rows the merge overwrote with audio and the padding rows looked nothing up) -- on top of the
+        lm_head term (tied: _head_wgrad wrote the range at the start of the backward) or of zeros (untied).  The last thing the
+        backward completes: its range closes grad_ranges()."""
+        ops, d = self.ops, st.dev
+        g = self.embed_view(self.proj.g)
+        if not self.geo.tied:
+            g.zero_()
+        if hasattr(ops, "embed_bwd"):
+            ops.embed_bwd(d["dx"], d["emb_rows"], d["emb_seg_start"], d["emb_seg_id"], g, st.M, st.M)
+        else:                                              # (operator sets without the kernel -- the CPU double: the same sum in torch)
+            rows = d["emb_rows"].long()
+            ok = rows >= 0
+            ids = torch.repeat_interleave(d["emb_seg_id"].long(), torch.diff(d["emb_seg_start"].long()))
+            g.index_add_(0, ids, d["dx"][rows[ok]])
+        if on_ready is not None:
+            on_ready(self._embed_tail_lo, self.embed_range[1])     # (with the alignment gap in front of it: grad_ranges)
 
     def backward_llm(self, st: StepState, span=None):
         """lm_head dgrad, final norm, 28 decoder layers (dgrad only: the LLM is frozen).  Leaves d(loss)/d(inputs_embeds)
@@ -1055,6 +1231,8 @@ class TasuModel:
         dvp = self._buf("dvp", (M, H * HD), f32)
         l_hi, l_lo = span if span is not None else (L, 0)
         # lm_head dgrad (K = Vpad: dlogits pad columns are zero) and final norm
+        if l_hi == L and self.embed_base is not None and geo.tied:
+            self._head_wgrad(st)
         if l_hi < L:
             pass                                               # a later span: the loss head ran with the first one
         elif d.get("labelled_only"):
@@ -1115,18 +1293,21 @@ class TasuModel:
         [norm.weight | norm.bias] (linear-silu) or [conv1d.weight | conv1d.bias] (cov1d-linear).  The ranges tile [0, numel)
         exactly."""
         pr = self.proj
-        end = pr.numel if self.lora is None else self.lora.base            # the projector's own tensors end here
+        end = self.proj_end                                                # the projector's own tensors end here
         # the adapters: one range per span of decoder layers, in the order the backward completes them (last layers first)
         head = [] if self.lora is None else [(self.lora.layer_range[hi - 1][0], self.lora.layer_range[lo][1]) for hi, lo in self.lora_spans()]
+        # use_emb: the embedding table's range comes last (its lookup term needs the finished dx); the 64-element alignment gap in
+        # front of it, if any, travels with it
+        tail = [] if self.embed_base is None else [(self._embed_tail_lo, self.embed_range[1])]
         if self.freeze_projector:
-            return head                                                    # the projector's part of the bucket is not touched
+            return head + tail                                             # the projector's part of the bucket is not touched
         if pr.is_ca:
-            return head + [(0, end)]
+            return head + [(0, end)] + tail
         o_w1, o_b1 = pr.offsets[pr.n_w1][0], pr.offsets[pr.n_b1][0]
         ld = pr.kin * pr.Kp
         rows = [pr.Hb * i // w1_chunks for i in range(w1_chunks + 1)]
         out = [(o_b1, end)] + [(o_w1 + r0 * ld, o_w1 + r1 * ld) for r0, r1 in zip(rows[:-1], rows[1:])]
-        return head + out + ([(0, o_w1)] if o_w1 > 0 else [])
+        return head + out + ([(0, o_w1)] if o_w1 > 0 else []) + tail
 
     def backward_projector(self, st: StepState, on_ready=None, w1_chunks=1):
         """Merge backward + projector backward (projector.py:149-151 / :38-49 reversed): wgrads land in the flat fp32 bucket.
@@ -1141,6 +1322,8 @@ class TasuModel:
         ranges = self.grad_ranges(w1_chunks)
         if self.lora is not None:
             ranges = ranges[len(self.lora_spans()):]   # (the adapters' ranges belong to backward_llm: run_backward reports them)
+        if self.embed_base is not None:
+            ranges = ranges[:-1]                       # (... and the embedding table's to backward_embed)
         # merge backward: gradient rows that hold audio -> projector output gradient
         Rap, K, Kp, Hb, Do = st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
         kKp = pr.kin * Kp                                     # input width of the first Linear
@@ -1271,6 +1454,8 @@ class TasuModel:
                     on_ready(self.lora.layer_range[hi - 1][0], self.lora.layer_range[lo][1])
             if not self.freeze_projector:
                 self.backward_projector(st, on_ready, w1_chunks)
+            if self.embed_base is not None:
+                self.backward_embed(st, on_ready)
 
     # ------------------------------------------------------------------------------------------ results
     def logits_view(self, st):

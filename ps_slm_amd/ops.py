@@ -485,6 +485,13 @@ class HipOps:
     def merge_bwd(self, dx, audio_rows, dproj, n, D):
         self._chk(self.lib.tasu_merge_bwd(_p(dx), _p(audio_rows), _p(dproj), n, D, self._stream()), "tasu_merge_bwd")
 
+    def embed_bwd(self, dx, rows, seg_start, seg_id, dtable, n_rows, n_seg):
+        """dtable[seg_id[s]] += sum of dx[rows[seg_start[s] : seg_start[s + 1]]] per segment (distinct ids; id < 0: skipped): the lookup
+        term of the embedding table's gradient (train_config.use_emb), summed in list order, bit-identical run to run."""
+        V, D = dtable.shape
+        self._chk(self.lib.tasu_embed_bwd(_p(dx), _p(rows), _p(seg_start), _p(seg_id), _p(dtable), dx.shape[0], n_rows, n_seg, V, D,
+                                          self._stream()), "tasu_embed_bwd")
+
     # ------------------------------------------------------------------ optimizer
     def adamw(self, p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale):
         self._chk(self.lib.tasu_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), float(lr), beta1, beta2, eps, wd,

@@ -42,6 +42,8 @@ from ps_slm_amd.model import Geometry, TasuModel  # noqa: E402
 
 logger = logging.getLogger(__name__)
 
+# the LLM's input embedding table in a checkpoint (train_config.use_emb): peft's name under slam_model_asr.llm, the prefix of lora.key_of
+EMBED_KEY = "llm.base_model.model.model.embed_tokens.weight"
 DEFAULT_SPEECH_TOKEN = "<speech>"
 DEFAULT_IGNORE_TOKEN = -100
 
@@ -113,8 +115,10 @@ def setup_encoder_tokenizer(model_config, geo):
 # ------------------------------------------------------------------------------------------------ geometry / weights
 def geometry_from_config(model_config, raw_features=False) -> Geometry:
     """HF config.json under llm_path when present; otherwise a named synthetic geometry
-    (``llm_path = synthetic:qwen2.5-1.5b | synthetic:qwen2.5-7b | synthetic:mid``)."""
+    (``llm_path = synthetic:qwen2.5-1.5b | synthetic:qwen2.5-7b | synthetic:mid | synthetic:mid-untied`` -- the last one is the mid
+    geometry with an lm_head of its own, the 7B's layout)."""
     path = str(model_config.get("llm_path", "") or "")
+    is_mid = path.lower() in ("synthetic:mid", "synthetic:mid-untied")    # the test geometry: encoder_dim / llm_dim overrides do not apply
     cfg_file = os.path.join(path, "config.json")
     if os.path.isfile(cfg_file):
         c = json.load(open(cfg_file))
@@ -131,9 +135,9 @@ def geometry_from_config(model_config, raw_features=False) -> Geometry:
             geo = Geometry.qwen25_1p5b()
         elif name in ("qwen2.5-7b", "7b"):
             geo = Geometry.qwen25_7b()
-        elif name == "mid":
+        elif name in ("mid", "mid-untied"):
             from ps_slm_amd.synthetic import MID_GEOMETRY
-            geo = Geometry.from_dict(MID_GEOMETRY)
+            geo = Geometry.from_dict(dict(MID_GEOMETRY, tied=name == "mid"))
         else:
             raise ValueError(f"unknown synthetic geometry {name!r}")
     else:
@@ -143,10 +147,10 @@ def geometry_from_config(model_config, raw_features=False) -> Geometry:
         # train_config.ctc_posterior=false (ps-slm.py:515-523): model_config.encoder_dim is the width of the encoder states the
         # projector reads; the CTC vocabulary (PSD still decides on the posterior) stays the encoder's own
         ed = model_config.get("encoder_dim", None)
-        if ed not in (None, geo.enc_dim) and path.lower() != "synthetic:mid":
+        if ed not in (None, geo.enc_dim) and not is_mid:
             raise ValueError(f"ctc_posterior=false: model_config.encoder_dim={ed} must be the encoder's output size {geo.enc_dim}")
         geo.proj_in = geo.enc_dim
-    elif model_config.get("encoder_dim", None) not in (None, geo.ctc_vocab) and path.lower() != "synthetic:mid":
+    elif model_config.get("encoder_dim", None) not in (None, geo.ctc_vocab) and not is_mid:
         geo.ctc_vocab = int(model_config.encoder_dim)
     if model_config.get("llm_dim", None) not in (None, geo.llm_dim):
         raise ValueError(f"model_config.llm_dim={model_config.llm_dim} does not match the LLM hidden size {geo.llm_dim}")
@@ -207,8 +211,8 @@ def model_factory(train_config, model_config, **kwargs):
         raise NotImplementedError("the MI355X path keeps the decoder's own weights frozen (freeze_llm=true: Multitask/scripts/"
                                   "finetune_deespeed_sensevoice.sh:84); with use_peft=true the LoRA adapters train, full fine-tuning of "
                                   "the LLM is not built")
-    if train_config.get("quantization", False) or train_config.get("use_emb", False):
-        raise NotImplementedError("train_config.quantization / use_emb (ps-slm.py:101-102, :119-123) are not built")
+    if train_config.get("quantization", False):
+        raise NotImplementedError("train_config.quantization (ps-slm.py:101-102: bitsandbytes 8-bit weights) is not built")
     if kwargs.get("peft_ckpt", None):
         raise NotImplementedError("peft_ckpt (a peft adapter DIRECTORY, ps-slm.py:110-112): load the adapters from the training "
                                   "checkpoint with ckpt_path instead -- it holds them under the reference's own key names")
@@ -223,6 +227,18 @@ def model_factory(train_config, model_config, **kwargs):
     # step is newer than their bf16 one: with use_fp16 = false, mixed_precision = false means "no bf16 anywhere" -- the alternate
     # projectors and the LoRA adapters train in fp32 as well, and a recipe without an fp32 step is refused here instead of training in bf16 behind a log line
     no_bf16 = fp32_mode and not train_config.get("mixed_precision", True)
+    # train_config.use_emb ("For llm input_embs", finetune_deespeed_sensevoice.sh:29,86): with use_peft the reference gives
+    # requires_grad = True to every LLM parameter whose name contains embed_tokens (ps-slm.py:119-123); the check sits inside the
+    # `elif train_config.use_peft` branch, so without use_peft the knob is never looked at
+    use_emb = bool(train_config.get("use_emb", False))
+    if use_emb and not use_peft:
+        logger.warning("train_config.use_emb is true but use_peft is false: the reference only looks at use_emb inside its use_peft "
+                       "branch (ps-slm.py:114-123) and ignores it here -- the embedding table stays frozen")
+        use_emb = False
+    if use_emb and no_bf16:
+        raise NotImplementedError("train_config.use_emb with use_fp16=false and mixed_precision=false: the fp32 training step has no "
+                                  "backward into the embedding table; use_emb trains on the bf16-autocast step (use_fp16=true, or "
+                                  "mixed_precision=true)")
     if no_bf16 and not f32_train_served:
         what = f"{projector} projector" + (" with LoRA adapters" if use_peft else "") + (" on raw encoder features" if raw else "")
         if raw:
@@ -293,6 +309,10 @@ def model_factory(train_config, model_config, **kwargs):
         core.enable_lora(LoraConfig.from_peft_config(train_config.get("peft_config", {}) or {}), seed=int(train_config.get("seed", 42)) + 7)
         logger.info("LoRA: r=%d alpha=%g dropout=%g on %s: %d adapter parameters", core.lora.cfg.r, core.lora.cfg.lora_alpha,
                     core.lora.cfg.lora_dropout, ",".join(core.lora.cfg.target_modules), core.lora.num_parameters())
+        if use_emb:
+            core.enable_embedding_training()
+            logger.info("use_emb: the LLM's input embedding table [%d, %d] trains%s", geo.llm_vocab, geo.llm_dim,
+                        " (tied: it is the lm_head too)" if geo.tied else " (the untied lm_head stays frozen)")
     model = slam_model_asr(core, tokenizer, setup_encoder_tokenizer(model_config, geo), train_config, model_config, **kwargs)
     ckpt_path = kwargs.get("ckpt_path", None)
     if ckpt_path is not None:
@@ -417,6 +437,8 @@ class slam_model_asr:
         if self.core.lora is not None:                 # use_peft=true: lora_A / lora_B of every adapted Linear, peft's key names
             for key, k in self.core.lora.names():
                 yield key, self.core.lora.view(flat, *k), True
+        if self.core.embed_base is not None:           # use_emb: the decoder's input embedding table [V, D]
+            yield EMBED_KEY, self.core.embed_view(flat), True
 
     def _trainable_views(self, flat):
         return [(n, v) for n, v, t in self._views(flat) if t]
@@ -427,7 +449,7 @@ class slam_model_asr:
         of the flat fp32 master buffer, ``requires_grad=True``, the SAME objects on every call (an optimizer built over them
         updates the masters in place; ``loss.backward()`` fills their ``.grad`` from the gradient bucket: ``_HipStep``)."""
         pr = self.core.proj
-        key = (pr.p.data_ptr(), pr.p.numel(), self.core.lora is not None, bool(self.core.freeze_projector))
+        key = (pr.p.data_ptr(), pr.p.numel(), self.core.lora is not None, bool(self.core.freeze_projector), self.core.embed_base)
         if self._leaves is None or self._leaves[0] != key:
             flat = pr.p.detach()
             self._leaves = (key, [(n, v.requires_grad_(t)) for n, v, t in self._views(flat)])
@@ -438,9 +460,10 @@ class slam_model_asr:
 
     def state_dict(self):
         """The trainable tensors (what the reference's checkpoint keeps: checkpoint_handler.py:169-182 saves with
-        exclude_frozen_parameters): the projector and, with use_peft, the adapters."""
+        exclude_frozen_parameters): the projector and, with use_peft, the adapters and -- use_emb -- the LLM's embedding table."""
         proj = {} if self.core.freeze_projector else self.core.projector_state_dict()
-        return {**proj, **self.core.lora_state_dict()}
+        emb = {} if self.core.embed_base is None else {EMBED_KEY: self.core.llm.embed.detach().clone()}
+        return {**proj, **self.core.lora_state_dict(), **emb}
 
     def load_state_dict(self, sd, strict=False):
         missing = []
@@ -458,6 +481,12 @@ class slam_model_asr:
                     self.core.lora.load(*k, sd[key])
                 else:
                     missing.append(key)
+        # the embedding table of a use_emb checkpoint is a value of the decoder: it loads into a model built without use_emb too
+        if EMBED_KEY in sd:
+            known.add(EMBED_KEY)
+            self.core.load_embed(sd[EMBED_KEY])
+        elif self.core.embed_base is not None:
+            missing.append(EMBED_KEY)
         if strict and missing:
             raise KeyError(f"missing keys {missing}")
         self.core.sync_projector_copies()

@@ -28,13 +28,16 @@ from .model import HD, StepState, rup
 def _transposed_weights(model):
     """fp32 W^T copies of the frozen decoder weights for the dgrad GEMMs (built once per model: +1x the fp32 weight bytes)."""
     llm = model.llm
-    if llm.f32.get("t") is None:
+    t = llm.f32.get("t")
+    if t is None or t.get("head") is None:                 # (head None: the tied embedding table changed, the layers' copies stand)
         Vp = rup(model.geo.llm_vocab, 64)
         head = llm.f32["head"]
         head_t = torch.zeros(head.shape[1], Vp, dtype=torch.float32, device=head.device)
         head_t[:, : head.shape[0]].copy_(head.t())
-        llm.f32["t"] = dict(layers=[{k: f[k].t().contiguous() for k in ("wqkv", "wo", "wgu", "wd")} for f in llm.f32["layers"]], head=head_t)
-    return llm.f32["t"]
+        if t is None:
+            t = llm.f32["t"] = dict(layers=[{k: f[k].t().contiguous() for k in ("wqkv", "wo", "wgu", "wd")} for f in llm.f32["layers"]])
+        t["head"] = head_t
+    return t
 
 
 def forward_train_fp32(model, st: StepState):

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 19
+#define TASU_ABI_VERSION 20
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -791,6 +791,35 @@ int tasu_f32_attn_bwd(const float* qkv, const float* dout, const int32_t* kstart
  * with it the row is split over 16 workgroups + a merge launch (a decode step's 64 rows are too few workgroups for one per row).        */
 int tasu_f32_logprob_topk(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, float* out_val,
                           int32_t* out_idx, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------ decoder weight gradients
+ * Full fine-tuning of the LLM (train_config.freeze_llm = false; Multitask/model/ps-slm.py:105-108 leaves every decoder parameter
+ * trainable).  csrc/wgrad.hip.
+ * tasu_gemm_tn_bf16: C[N, K] (fp32, leading dimension ldc) = (accumulate == 0) or += sum_r A[r, n] . B[r, k] -- a Linear's
+ * dW = dY^T X with A = dY [R, N] and B = X [R, K], both bf16 and ROW-major as the training step leaves them: the token rows are the
+ * reduction and no transposed copy is made (hardware transpose reads from LDS, 128 x 128 tiles).  nsplit > 1 cuts the rows into
+ * that many ranges of whole 64-row stages, one fp32 slab [N, K] each in ws, summed in slab order by a second launch (deterministic;
+ * for outputs with too few tiles to fill the chip: tasu_gemm_tn_bf16_split gives the count to use, host code, -1 on bad sizes).
+ * Rules (anything else: TASU_ERR_ARG before any launch): R >= 1 (any); N % 8 == 0 and K % 8 == 0; lda >= N, ldb >= K, both % 8 == 0;
+ * ldc >= K, ldc % 4 == 0; A, B, C (and ws) 16-byte aligned; 1 <= nsplit <= min(TASU_GEMM_TN_MAX_SPLIT, ceil(R / 64)); nsplit > 1
+ * needs ws_floats >= nsplit * N * K.  Elements of C outside [N, K] are never written.  Products of bf16 values are exact in fp32;
+ * the sum runs in row order up to the order of the 32 products inside one MFMA, then over the slabs.
+ * tasu_rmsnorm_wgrad: dw[j] = or += sum_r dy[r, j] . x[xr(r), j] . rstd[r] -- the weight gradient of Qwen2RMSNorm with dy (bf16
+ * [R, D]), x (fp32) and rstd exactly as tasu_rmsnorm_bwd reads them; xr(r) = r, or src_rows[r] when src_rows is given (the
+ * row-compacted form of tasu_rmsnorm_bwd_rows: dy / rstd compact, x indexed; rows with src_rows[r] < 0 are skipped).  Two stages
+ * (TASU_RMS_WGRAD_SPLIT interleaved row slabs into ws, then their sum in slab order): deterministic.  ws: TASU_RMS_WGRAD_SPLIT * D
+ * floats; D % 4 == 0.
+ * tasu_colsum_bf16_split: out[c] = or += sum_r x[r, c] of a bf16 [R, C] matrix (leading dimension ld) by the same two stages -- the
+ * q|k|v bias gradient over thousands of token rows, where tasu_colsum_bf16's one block per 64 columns walks all rows alone.
+ * ws: TASU_RMS_WGRAD_SPLIT * C floats; C % 4 == 0, ld % 4 == 0, ld >= C.                                                       */
+#define TASU_GEMM_TN_MAX_SPLIT 16
+#define TASU_RMS_WGRAD_SPLIT 64
+int tasu_gemm_tn_bf16_split(int R, int N, int K);
+int tasu_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int R, int N, int K, int accumulate, int nsplit,
+                      float* ws, int64_t ws_floats, void* stream);
+int tasu_rmsnorm_wgrad(const void* dy_bf16, const float* x, const float* rstd, const int32_t* src_rows, float* dw, float* ws, int R, int D,
+                       int accumulate, void* stream);
+int tasu_colsum_bf16_split(const void* x, int ld, float* out, float* ws, int R, int C, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------ FLAC (host)
  * The reference reads ``.flac`` entries with torchaudio.load (speech_dataset_large.py:123-127: [C, T] float

@@ -166,9 +166,14 @@ PROTOTYPES.update({
     "tasu_f32_transpose": [vp, i32, vp, i32, i32, i32, i32, vp],
     "tasu_f32_gather_rows": [vp, vp, vp, i32, i32, vp],
     "tasu_f32_attn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    # the decoder's own weight gradients (csrc/wgrad.hip)
+    "tasu_gemm_tn_bf16_split": [i32, i32, i32],
+    "tasu_gemm_tn_bf16": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp],
+    "tasu_rmsnorm_wgrad": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "tasu_colsum_bf16_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

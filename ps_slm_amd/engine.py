@@ -232,7 +232,7 @@ class TasuEngine:
             self.core.run_backward(st)
             self._g_acc.add_(self.core.proj.g, alpha=1.0 / (self.ga * self.ga))
             if self.micro_steps % self.ga == 0 and self.exchange:
-                lo0 = self.core.lora.base if (self.core.freeze_projector and self.core.lora is not None) else 0
+                lo0 = self.core.trainable_lo
                 self._issue(self._g_acc, lo0, self._g_acc.numel())
             return
         if self.exchange:
@@ -251,7 +251,7 @@ class TasuEngine:
         self.global_steps += 1
         lr = self.get_lr()[0]
         g = self._g_acc if self.ga > 1 else pr.g
-        lo0 = self.core.lora.base if (self.core.freeze_projector and self.core.lora is not None) else 0   # frozen projector: adapters only
+        lo0 = self.core.trainable_lo   # frozen projector: adapters only
         ranges = self._pending if self._pending else [(lo0, pr.numel, None)]
         for lo, hi, work in ranges:
             if work is not None:
@@ -315,8 +315,9 @@ class TasuEngine:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg)
         return t.tolist()
 
-    # ---- checkpoint (the trainable tensors -- projector, + LoRA adapters with use_peft -- under the reference's key names:
-    #      checkpoint_handler.py:169-182, ps-slm.py:163-170)
+    # ---- checkpoint (the trainable tensors -- projector, + LoRA adapters with use_peft, or -- freeze_llm=false -- every tensor of the
+    #      decoder as llm.model.* / llm.lm_head.weight in fp32 -- under the reference's key names: checkpoint_handler.py:169-182, :214,
+    #      ps-slm.py:163-170)
     def save_checkpoint(self, path):
         if self.rank == 0:
             torch.save({k: v.cpu() for k, v in self.module.state_dict().items()}, path)          # the trainable tensors

@@ -472,6 +472,7 @@ class TasuModel:
         # embed_version counts changes of the table's values (optimizer step, load) for everything that caches a copy of it
         self.embed_base = None
         self.embed_version = 0
+        self.full_ft = None            # ps_slm_amd.full_ft.LLMTrainables once enable_llm_training() ran (freeze_llm=false without use_peft)
         self.freeze_projector = False  # train_config.freeze_projector (ps-slm.py:50-54): the projector's weight gradients, exchange and
                                        # optimizer update are skipped; only the adapters train (the plugin refuses it without use_peft)
         self.raw_features = geo.proj_in not in (0, geo.ctc_vocab)   # ctc_posterior=false: the projector reads encoder states
@@ -489,6 +490,8 @@ class TasuModel:
         self.llm.load_reference_state_dict(sd)
         if self.lora is not None:
             self.lora.build_ext(self.llm)                  # [W | B] copies of the adapted Linears follow the new base weights
+        if self.full_ft is not None:
+            self.full_ft.adopt(sd)                         # the new decoder moves into the bucket, masters from the fp32 tensors
         if self.embed_base is not None:
             self._adopt_embed()                            # the new table moves into the bucket
         for n in self.proj.names:
@@ -512,6 +515,8 @@ class TasuModel:
         self.llm.init_random(seed)
         if self.lora is not None:
             self.lora.build_ext(self.llm)
+        if self.full_ft is not None:
+            self.full_ft.adopt()
         if self.embed_base is not None:
             self._adopt_embed()
         self.init_projector_default(seed + 1)
@@ -569,8 +574,57 @@ class TasuModel:
         self.proj.refresh_working_copies(self.ops)
         if self.lora is not None:
             self.lora.refresh_working_copies(self.ops)
+        if self.full_ft is not None:
+            self.full_ft.refresh_working_copies(self.ops)
         if self.embed_base is not None:
             self._embed_changed()
+
+    # ---- train_config.freeze_llm = false: every tensor of the decoder trains (ps-slm.py:105-108; ps_slm_amd/full_ft.py)
+    def enable_llm_training(self, sd=None):
+        """freeze_llm=false without use_peft: the fp32 masters of all decoder tensors join the trainable bucket behind the projector,
+        [projector | norm | untied head | layers, last first | embedding table]; ``LLMWeights``' tensors become views of the bucket
+        (ps_slm_amd/full_ft.py).  The table goes last through enable_embedding_training(): the use_emb mechanism, reused.  ``sd``:
+        the decoder's fp32 tensors under the reference's names, when the caller still has them (the masters then start from them
+        instead of from the bf16 copies).  Call before an engine is built on the model (the bucket grows)."""
+        from .full_ft import LLMTrainables
+        if self.full_ft is not None:
+            raise RuntimeError("the LLM is already trainable on this model")
+        if self.lora is not None or self.embed_base is not None:
+            raise RuntimeError("enable_llm_training with LoRA / use_emb: freeze_llm=false with use_peft=true is the LoRA recipe (peft freezes the base weights)")
+        if self.arith_train == "fp32":
+            raise NotImplementedError("freeze_llm=false on the fp32 training step: ps_slm_amd/train_fp32.py has no weight gradients of the "
+                                      "decoder (full fine-tuning runs on the bf16-autocast step: use_fp16=true)")
+        ft = LLMTrainables(self)
+        self.enable_embedding_training()                   # [.. | embedding table]: lookup term + the tied head's term, as with use_emb
+        self.full_ft = ft
+        if self.llm.layers:
+            ft.adopt(sd)
+            self.sync_projector_copies()
+
+    def load_llm_tensors(self, sd):
+        """A fully fine-tuned decoder out of a checkpoint (``llm.model.*`` and, untied, ``llm.lm_head.weight``: every tensor of
+        Qwen2ForCausalLM in fp32) into a model that keeps the LLM FROZEN: the tensors replace the frozen weights in every layout the
+        model holds (bf16 pairs, the fp32 copies of use_fp16=false), as a load of the base model would.  With tied embeddings a
+        lm_head key is ignored."""
+        from .full_ft import EMBED_KEY, HEAD_KEY, NORM_KEY, PRE
+        geo = self.geo
+        mods = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.o_proj.weight", "mlp.gate_proj.weight",
+                "mlp.up_proj.weight", "mlp.down_proj.weight") + tuple(f"self_attn.{m}_proj.{k}" for m in "qkv" for k in ("weight", "bias"))
+        need = [f"{PRE}model.layers.{l}.{m}" for l in range(geo.llm_layers) for m in mods] + [NORM_KEY, EMBED_KEY] + ([] if geo.tied else [HEAD_KEY])
+        lacking = [k for k in need if k not in sd]
+        if lacking:
+            raise KeyError(f"a checkpoint of the fine-tuned LLM must hold all of its tensors; missing {lacking[:4]}{' ...' if len(lacking) > 4 else ''}")
+        sd = {k: v for k, v in sd.items() if not (geo.tied and k == HEAD_KEY)}
+        self.llm.load_reference_state_dict(sd)
+        self.llm._ca_e = self.llm._ca_et = None
+        if self.lora is not None:
+            self.lora.build_ext(self.llm)
+            self.lora._merged = self.lora._merged32 = None    # the decode-time W + s B A were built on the old base weights
+        if self.embed_base is not None:
+            self._adopt_embed()
+        self.embed_version += 1
+        self._graphs.clear()
+        self._dec_graphs.clear()
 
     # ---- train_config.use_emb: the decoder's input embedding table as a trainable tensor (ps-slm.py:119-123)
     def enable_embedding_training(self):
@@ -597,7 +651,18 @@ class TasuModel:
         """Where the projector's own tensors end in the bucket (the adapters, else the embedding table, else nothing follows)."""
         if self.lora is not None:
             return self.lora.base
+        if self.full_ft is not None:
+            return self.full_ft.lo
         return self.proj.numel if self.embed_base is None else self._embed_tail_lo
+
+    @property
+    def trainable_lo(self):
+        """Where the trained part of the bucket begins: 0, or -- frozen projector -- the adapters' / the decoder's first element."""
+        if not self.freeze_projector:
+            return 0
+        if self.lora is not None:
+            return self.lora.base
+        return self.full_ft.lo if self.full_ft is not None else 0
 
     @property
     def embed_range(self):
@@ -1076,8 +1141,17 @@ class TasuModel:
         xn = self._buf("xn_llm", (M, D), bf)
         act = self._buf("act", (M, I), bf)
         lora = self._lora_run
+        ft = self.full_ft
+        # full fine-tuning keeps the GEMM operands of every layer for the weight gradients (the normed inputs and the SwiGLU output;
+        # the frozen step overwrites one buffer), and runs no compact tail: the last layer's MLP weights want all rows' operands in
+        # the same [M, .] form as every other layer's
+        keep = ft is not None and need_backward
+        if keep:
+            xn_l = self._buf("ft_xn", (2 * L, M, D), bf)
+            act_l = self._buf("ft_act", (L, M, I), bf)
+            d.update(ft_xn=xn_l, ft_act=act_l)
         tail = bool(self.tail_rows and compute_loss and need_backward and not self.keep_logits and logits_rows != "none"
-                    and "lab_rows" in d and st.nLp > 0 and lora is None)
+                    and "lab_rows" in d and st.nLp > 0 and lora is None and ft is None)
         drop = lora is not None and lora._drop_on(self.training)
         if drop:
             ops.rng_advance(self.lora.rng)                     # new masks for this micro-step (a launch: graph replays advance too)
@@ -1088,6 +1162,8 @@ class TasuModel:
                 lora.layer_fwd(st, l, w, fb, drop)
                 continue
             x_in, x_mid, x_out = xs[2 * l], xs[2 * l + 1], xs[2 * l + 2]
+            if keep:                                           # this layer's own operand buffers
+                xn, act = xn_l[2 * l], act_l[l]
             ops.rmsnorm_fwd(x_in, w["ln1"], xn, rstd[2 * l], geo.rms_eps)
             ops.gemm_qkv_rope(xn, w["wqkv"], w["bqkv"], qkv[l], cos, sin, M, H, G, D)      # bias + RoPE in the GEMM's epilogue
             ops.attn_fwd(qkv[l], None, d["key_mask"], ao[l], lse[l], B, S, H, G, scale, True)
@@ -1107,6 +1183,8 @@ class TasuModel:
                 ops.gemm(act_t, w["wd"], xout_t, n, D, I, resid=xmid_t, mode=GEMM_RESID)
                 d.update(rstd_tail=rstd_t, gu_tail=gu_t, xout_tail=xout_t)
                 continue
+            if keep:
+                xn = xn_l[2 * l + 1]
             ops.rmsnorm_fwd(x_mid, w["ln2"], xn, rstd[2 * l + 1], geo.rms_eps)
             ops.gemm_gate_up_swiglu(xn, w["wgu"], gu[l], act, M, I, D)          # gate|up projection + SwiGLU epilogue
             ops.gemm(act, w["wd"], x_out, M, D, I, resid=x_mid, mode=GEMM_RESID)
@@ -1115,6 +1193,8 @@ class TasuModel:
             return
         if compute_loss and need_backward and not self.keep_logits:
             return self._loss_on_labelled_rows(st)
+        if keep:
+            xn = self._buf("xn_llm", (M, D), bf)               # (not the last layer's kept operand)
         ops.rmsnorm_fwd(xs[2 * L], llm.norm, xn, rstd[2 * L], geo.rms_eps)
         logits = self._buf("logits", (M, Vp), bf)
         ops.gemm(xn, llm.head, logits, M, V, D)
@@ -1172,7 +1252,7 @@ class TasuModel:
         if self.embed_base is not None:
             self.backward_embed(st, on_ready)
 
-    def _head_wgrad(self, st):
+    def _head_wgrad(self, st, dst=None):
         """use_emb with tied embeddings: the lm_head's weight gradient dW = dlogits^T h is the second term of the table's gradient
         (h: the final-normed rows that fed the lm_head GEMM -- the compact labelled rows in the throughput mode).  fp32, on the MFMA
         GEMM behind the transposes the projector's dW1 uses, straight into (overwriting) the table's range of the bucket; rows
@@ -1185,7 +1265,8 @@ class TasuModel:
         h_t = self._buf("emb_h_t", (D, npad), torch.bfloat16)
         ops.transpose(d["dlogits"], dl_t, n, Vp, npad, Vp)
         ops.transpose(d["xn_head"], h_t, n, D, npad, D)
-        ops.gemm(dl_t, h_t, self.embed_view(self.proj.g), V, D, npad, mode=GEMM_F32)
+        # (dst: the untied lm_head's own range when the whole decoder trains -- the same product)
+        ops.gemm(dl_t, h_t, self.embed_view(self.proj.g) if dst is None else dst, V, D, npad, mode=GEMM_F32)
 
     def backward_embed(self, st, on_ready=None):
         """use_emb: the lookup term of the table's gradient -- every text row of dx = d(loss)/d(inputs_embeds) added into the row of
@@ -1231,8 +1312,11 @@ class TasuModel:
         dvp = self._buf("dvp", (M, H * HD), f32)
         l_hi, l_lo = span if span is not None else (L, 0)
         # lm_head dgrad (K = Vpad: dlogits pad columns are zero) and final norm
+        ft = self.full_ft
         if l_hi == L and self.embed_base is not None and geo.tied:
             self._head_wgrad(st)
+        elif l_hi == L and ft is not None:
+            self._head_wgrad(st, ft.view(self.proj.g, "head"))
         if l_hi < L:
             pass                                               # a later span: the loss head ran with the first one
         elif d.get("labelled_only"):
@@ -1261,9 +1345,13 @@ class TasuModel:
                 ops.gemm(dgu_t, w["wgu_t"], dn_c, n, D, 2 * I)
                 ops.rmsnorm_bwd_rows_resid(dn_c, xs[2 * L - 1], w["ln2"], d["rstd_tail"], d["lab_slot"], dx_t, dx, dxb)
             else:
+                if ft is not None:                             # model.norm.weight: compact dy / rstd, x by the labelled rows' index
+                    ft.norm_wgrad(dn_c, xs[2 * L], d["rstd_lab"], "norm", None, src_rows=d["lab_rows"])
                 ops.rmsnorm_bwd_rows(dn_c, xs[2 * L], llm.norm, d["rstd_lab"], d["lab_slot"], dx, dxb)
         else:
             ops.gemm(d["dlogits"], llm.head_t, dn, M, D, Vp)
+            if ft is not None:
+                ft.norm_wgrad(dn, xs[2 * L], rstd[2 * L], "norm", None)
             ops.rmsnorm_bwd(dn, xs[2 * L], llm.norm, rstd[2 * L], dx, dxb, False)
         lora = self._lora_run
         bb = dict(dx=dx, dxb=dxb, dn=dn, dact=dact, dgu=dgu, dao=dao, delta=delta, dqkv=dqkv, dkp=dkp, dvp=dvp)
@@ -1273,15 +1361,28 @@ class TasuModel:
                 lora.layer_bwd(st, l, w, bb, bool(getattr(st, "lora_drop", False)))
                 continue
             x_in, x_mid = xs[2 * l], xs[2 * l + 1]
+            # full fine-tuning (ft; no compact tail then): every weight gradient sits next to the dgrad that consumes the same dY
             if not (l == L - 1 and "xout_tail" in d):          # (the compact tail above has done the last layer's MLP)
                 ops.gemm_dswiglu(dxb, w["wd_t"], d["gu"][l], dgu, dact, M, I, D)
+                if ft is not None:
+                    ft.wgrad(dxb, d["ft_act"][l], "wd", l)
                 ops.gemm(dgu, w["wgu_t"], dn, M, D, 2 * I)
+                if ft is not None:
+                    ft.wgrad(dgu, d["ft_xn"][2 * l + 1], "wgu", l)
+                    ft.norm_wgrad(dn, x_mid, rstd[2 * l + 1], "ln2", l)
                 ops.rmsnorm_bwd(dn, x_mid, w["ln2"], rstd[2 * l + 1], dx, dxb, True)
+            if ft is not None:
+                ft.wgrad(dxb, d["ao"][l], "wo", l)
             ops.gemm(dxb, w["wo_t"], dao, M, H * HD, D)
             # delta = rowsum(dO . O), dQ, dK / dV and the rotary embedding's backward behind one entry point: the single-pass kernels
             # for Spad <= 256 (delta inside the kernel; dkp / dvp = one fp32 partial per query head), else the tiled kernels
             ops.attn_bwd_fused(d["qkv"][l], d["key_mask"], dao, d["ao"][l], d["lse"][l], delta, cos, sin, dqkv, dkp, dvp, B, S, H, G, scale, True)
+            if ft is not None:
+                ft.wgrad(dqkv, d["ft_xn"][2 * l], "wqkv", l)
+                ft.bias_wgrad(dqkv, "bqkv", l)                 # q|k|v bias: dqkv behind the RoPE backward
             ops.gemm(dqkv, w["wqkv_t"], dn, M, D, LDQ)
+            if ft is not None:
+                ft.norm_wgrad(dn, x_in, rstd[2 * l], "ln1", l)
             ops.rmsnorm_bwd(dn, x_in, w["ln1"], rstd[2 * l], dx, dxb, True)
         if lora is not None:
             lora.join()                                        # the adapters' weight-gradient chains (side stream) are back
@@ -1296,6 +1397,8 @@ class TasuModel:
         end = self.proj_end                                                # the projector's own tensors end here
         # the adapters: one range per span of decoder layers, in the order the backward completes them (last layers first)
         head = [] if self.lora is None else [(self.lora.layer_range[hi - 1][0], self.lora.layer_range[lo][1]) for hi, lo in self.lora_spans()]
+        if self.full_ft is not None:                                       # the decoder's own tensors: [norm | head], then layer by layer
+            head = self.full_ft.grad_ranges()
         # use_emb: the embedding table's range comes last (its lookup term needs the finished dx); the 64-element alignment gap in
         # front of it, if any, travels with it
         tail = [] if self.embed_base is None else [(self._embed_tail_lo, self.embed_range[1])]
@@ -1322,6 +1425,8 @@ class TasuModel:
         ranges = self.grad_ranges(w1_chunks)
         if self.lora is not None:
             ranges = ranges[len(self.lora_spans()):]   # (the adapters' ranges belong to backward_llm: run_backward reports them)
+        if self.full_ft is not None:
+            ranges = ranges[len(self.full_ft.grad_ranges()):]   # (... and so do the decoder's own)
         if self.embed_base is not None:
             ranges = ranges[:-1]                       # (... and the embedding table's to backward_embed)
         # merge backward: gradient rows that hold audio -> projector output gradient
@@ -1445,6 +1550,9 @@ class TasuModel:
         else:
             if self.lora is None:
                 self._graphed(self._shape_key(st, "bwd_llm"), lambda: self.backward_llm(st), st)
+                if self.full_ft is not None:         # the decoder's own gradients: complete behind the graph, reported in bucket order
+                    for lo, hi in self.full_ft.grad_ranges():
+                        on_ready(lo, hi)
             else:
                 # use_peft: the decoder's backward as one graph per span of layers; after each span its adapters' gradients --
                 # a contiguous range of the bucket (the layers are laid out in completion order) -- go on the wire under the

@@ -16,6 +16,7 @@ from . import _lib
 GEMM_BF16, GEMM_F32, GEMM_RESID = 0, 1, 2
 GEMM_WS_BYTES = (64 << 20) + 4096 * 4          # tasu_gemm_nt_bf16_ws workspace: counters + split-K partial tiles
 LN_BWD_SPLIT = 16
+RMS_WGRAD_SPLIT = 64                           # TASU_RMS_WGRAD_SPLIT: row slabs of tasu_rmsnorm_wgrad's workspace
 
 
 class F32Fragments:
@@ -313,6 +314,35 @@ class HipOps:
 
     def colsum(self, x, out, R, Cn):
         self._chk(self.lib.tasu_colsum_bf16(_p(x), x.stride(0), _p(out), R, Cn, self._stream()), "tasu_colsum_bf16")
+
+    # ------------------------------------------------------------------ the decoder's own weight gradients (csrc/wgrad.hip)
+    def gemm_tn_split(self, R, N, K):
+        """How many row ranges gemm_tn should cut R into for this output (host code): the caller sizes ``ws`` with it."""
+        return int(self.lib.tasu_gemm_tn_bf16_split(R, N, K))
+
+    def gemm_tn(self, a, b, c, R, N, K, accumulate=False, nsplit=1, ws=None):
+        """c[N, K] (fp32) = or += a[:R, :N]^T @ b[:R, :K]: a Linear's weight gradient dW = dY^T X from the row-major bf16 tensors
+        of the step, no transposed copies.  ``nsplit`` > 1: that many row ranges, fp32 slabs in ``ws`` (nsplit * N * K floats),
+        summed in slab order."""
+        self._chk(self.lib.tasu_gemm_tn_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0), R, N, K, int(accumulate),
+                                             int(nsplit), _p(ws), 0 if ws is None else ws.numel(), self._stream()), "tasu_gemm_tn_bf16")
+
+    def rmsnorm_wgrad(self, dy, x, rstd, dw, ws, src_rows=None, accumulate=False):
+        """dw[j] = or += sum_r dy[r, j] * x[r (or src_rows[r]), j] * rstd[r]: the RMSNorm weight gradient from what rmsnorm_bwd
+        (or, with ``src_rows``, rmsnorm_bwd_rows) reads.  ``ws``: RMS_WGRAD_SPLIT * D floats."""
+        R, D = dy.shape
+        if ws.numel() < RMS_WGRAD_SPLIT * D:
+            raise TasuOpError(f"rmsnorm_wgrad: workspace of {ws.numel()} floats, {RMS_WGRAD_SPLIT * D} needed")
+        self._chk(self.lib.tasu_rmsnorm_wgrad(_p(dy), _p(x), _p(rstd), _p(src_rows), _p(dw), _p(ws), R, D, int(accumulate),
+                                              self._stream()), "tasu_rmsnorm_wgrad")
+
+    def colsum_split(self, x, out, ws, R, Cn, accumulate=False):
+        """out[:Cn] = or += column sums of the bf16 x[:R, :Cn] in two stages (``ws``: RMS_WGRAD_SPLIT * Cn floats): bias gradients over
+        thousands of rows."""
+        if ws.numel() < RMS_WGRAD_SPLIT * Cn:
+            raise TasuOpError(f"colsum_split: workspace of {ws.numel()} floats, {RMS_WGRAD_SPLIT * Cn} needed")
+        self._chk(self.lib.tasu_colsum_bf16_split(_p(x), x.stride(0), _p(out), _p(ws), R, Cn, int(accumulate), self._stream()),
+                  "tasu_colsum_bf16_split")
 
     # ------------------------------------------------------------------ rope + attention
     def rope_table(self, pos, cos, sin, head_dim, theta):

@@ -44,6 +44,7 @@ logger = logging.getLogger(__name__)
 
 # the LLM's input embedding table in a checkpoint (train_config.use_emb): peft's name under slam_model_asr.llm, the prefix of lora.key_of
 EMBED_KEY = "llm.base_model.model.model.embed_tokens.weight"
+from ps_slm_amd.full_ft import EMBED_KEY as FT_EMBED_KEY, is_llm_key  # noqa: E402  (a fully fine-tuned decoder: the reference's own module names)
 DEFAULT_SPEECH_TOKEN = "<speech>"
 DEFAULT_IGNORE_TOKEN = -100
 
@@ -207,10 +208,18 @@ def model_factory(train_config, model_config, **kwargs):
                                   "Multitask/scripts/finetune_deespeed_sensevoice.sh:25), 'linear' (EncoderProjectorConcat, "
                                   "Multitask/model/projector.py:28-49), 'cov1d-linear' (EncoderProjectorCov1d, :53-73) and "
                                   "'cross-attention' (EncoderProjectorCTCCA, :104-126); q-former / simple_linear are not built")
-    if not train_config.get("freeze_llm", True):
-        raise NotImplementedError("the MI355X path keeps the decoder's own weights frozen (freeze_llm=true: Multitask/scripts/"
-                                  "finetune_deespeed_sensevoice.sh:84); with use_peft=true the LoRA adapters train, full fine-tuning of "
-                                  "the LLM is not built")
+    # train_config.freeze_llm = false (the dataclass default, aispeech_asr_config.py:116): setup_llm leaves every decoder parameter
+    # trainable (ps-slm.py:105-108).  With use_peft=true peft freezes the base weights itself (the knob's help text says so): the LoRA
+    # recipe, as with freeze_llm=true.  Without it the whole decoder trains (ps_slm_amd/full_ft.py), on the bf16-autocast step only
+    full_ft = not train_config.get("freeze_llm", True)
+    if full_ft and train_config.get("use_peft", False):
+        logger.warning("train_config.freeze_llm is false with use_peft=true: peft freezes the base weights itself -- the LoRA recipe, "
+                       "exactly what freeze_llm=true builds")
+        full_ft = False
+    if full_ft and not train_config.get("use_fp16", False):
+        raise NotImplementedError("train_config.freeze_llm=false with use_fp16=false: the fp32 training step has no weight gradients of "
+                                  "the decoder; full fine-tuning of the LLM runs on the bf16-autocast step -- set use_fp16=true (or "
+                                  "freeze_llm=true: Multitask/scripts/finetune_deespeed_sensevoice.sh:84)")
     if train_config.get("quantization", False):
         raise NotImplementedError("train_config.quantization (ps-slm.py:101-102: bitsandbytes 8-bit weights) is not built")
     if kwargs.get("peft_ckpt", None):
@@ -300,8 +309,8 @@ def model_factory(train_config, model_config, **kwargs):
     # train_config.freeze_projector (the shipped script carries the knob, finetune_deespeed_sensevoice.sh:46,80): the reference
     # honours it for the linear-silu projector only (ps-slm.py:47-54) and then trains whatever else requires a gradient
     frozen_proj = bool(train_config.get("freeze_projector", False)) and projector == "linear-silu"
-    if frozen_proj and not train_config.get("use_peft", False):
-        raise ValueError("freeze_projector=true with use_peft=false leaves nothing to train (freeze_llm and freeze_encoder are fixed "
+    if frozen_proj and not train_config.get("use_peft", False) and not full_ft:
+        raise ValueError("freeze_projector=true with use_peft=false and freeze_llm=true leaves nothing to train (the encoder is frozen "
                          "here): the reference's optimizer would receive an empty parameter list")
     core.freeze_projector = frozen_proj
     if train_config.get("use_peft", False):
@@ -313,6 +322,11 @@ def model_factory(train_config, model_config, **kwargs):
             core.enable_embedding_training()
             logger.info("use_emb: the LLM's input embedding table [%d, %d] trains%s", geo.llm_vocab, geo.llm_dim,
                         " (tied: it is the lm_head too)" if geo.tied else " (the untied lm_head stays frozen)")
+    if full_ft:
+        core.enable_llm_training(None if llm_path.startswith("synthetic:") else sd)
+        logger.info("freeze_llm=false: the decoder's %d tensors (%d parameters with the embedding table) train%s",
+                    len(core.full_ft.offsets), core.full_ft.num_parameters() + geo.llm_vocab * geo.llm_dim,
+                    " next to the projector" if not frozen_proj else "; the projector is frozen")
     model = slam_model_asr(core, tokenizer, setup_encoder_tokenizer(model_config, geo), train_config, model_config, **kwargs)
     ckpt_path = kwargs.get("ckpt_path", None)
     if ckpt_path is not None:
@@ -437,7 +451,11 @@ class slam_model_asr:
         if self.core.lora is not None:                 # use_peft=true: lora_A / lora_B of every adapted Linear, peft's key names
             for key, k in self.core.lora.names():
                 yield key, self.core.lora.view(flat, *k), True
-        if self.core.embed_base is not None:           # use_emb: the decoder's input embedding table [V, D]
+        if self.core.full_ft is not None:              # freeze_llm=false: every tensor of Qwen2ForCausalLM, the reference's module names
+            for key, v in self.core.full_ft.named_views(flat):
+                yield key, v, True
+            yield FT_EMBED_KEY, self.core.embed_view(flat), True
+        elif self.core.embed_base is not None:         # use_emb: the decoder's input embedding table [V, D]
             yield EMBED_KEY, self.core.embed_view(flat), True
 
     def _trainable_views(self, flat):
@@ -449,7 +467,8 @@ class slam_model_asr:
         of the flat fp32 master buffer, ``requires_grad=True``, the SAME objects on every call (an optimizer built over them
         updates the masters in place; ``loss.backward()`` fills their ``.grad`` from the gradient bucket: ``_HipStep``)."""
         pr = self.core.proj
-        key = (pr.p.data_ptr(), pr.p.numel(), self.core.lora is not None, bool(self.core.freeze_projector), self.core.embed_base)
+        key = (pr.p.data_ptr(), pr.p.numel(), self.core.lora is not None, bool(self.core.freeze_projector), self.core.embed_base,
+               self.core.full_ft is not None)
         if self._leaves is None or self._leaves[0] != key:
             flat = pr.p.detach()
             self._leaves = (key, [(n, v.requires_grad_(t)) for n, v, t in self._views(flat)])
@@ -462,6 +481,8 @@ class slam_model_asr:
         """The trainable tensors (what the reference's checkpoint keeps: checkpoint_handler.py:169-182 saves with
         exclude_frozen_parameters): the projector and, with use_peft, the adapters and -- use_emb -- the LLM's embedding table."""
         proj = {} if self.core.freeze_projector else self.core.projector_state_dict()
+        if self.core.full_ft is not None:              # freeze_llm=false: checkpoint_handler.py:214 saves the LLM, fp32 masters
+            return {**proj, **self.core.full_ft.state_dict(), FT_EMBED_KEY: self.core.llm.embed.detach().clone()}
         emb = {} if self.core.embed_base is None else {EMBED_KEY: self.core.llm.embed.detach().clone()}
         return {**proj, **self.core.lora_state_dict(), **emb}
 
@@ -485,8 +506,26 @@ class slam_model_asr:
         if EMBED_KEY in sd:
             known.add(EMBED_KEY)
             self.core.load_embed(sd[EMBED_KEY])
-        elif self.core.embed_base is not None:
+        elif self.core.embed_base is not None and self.core.full_ft is None:
             missing.append(EMBED_KEY)
+        # a fully fine-tuned decoder (freeze_llm=false): its tensors are values of the decoder too -- into the masters of a model that
+        # trains them, or in place of the frozen weights of one that does not (with tied embeddings a lm_head key is ignored)
+        llm_keys = [k for k in sd if is_llm_key(k)]
+        known.update(llm_keys)
+        ft = self.core.full_ft
+        if ft is not None:
+            have = set(llm_keys)
+            for key, _ in ft.named_views(self.core.proj.p):
+                if key in have:
+                    ft.load(key, sd[key])
+                else:
+                    missing.append(key)
+            if FT_EMBED_KEY in have:
+                self.core.load_embed(sd[FT_EMBED_KEY])
+            else:
+                missing.append(FT_EMBED_KEY)
+        elif llm_keys:
+            self.core.load_llm_tensors({k: sd[k] for k in llm_keys})
         if strict and missing:
             raise KeyError(f"missing keys {missing}")
         self.core.sync_projector_copies()

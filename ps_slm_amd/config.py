@@ -140,6 +140,12 @@ class RunConfig(_Section):
     deepspeed_config: str = ""
     decode_log: str = "output/decode_log"
     peft_ckpt: Optional[str] = None
+    # resume (Multitask/finetune_deepspeed.py:32-37 declares the first two and never reads them; here they are the save_dir and tag of
+    # TasuEngine.save_state / load_state) and how often the training state is written, in optimizer steps (0: only where the loop
+    # writes pytorch_model.bin after a validation improvement)
+    deepspeed_ckpt_path: Optional[str] = None
+    deepspeed_ckpt_id: Optional[str] = None
+    state_interval: int = 0
 
 
 def _coerce(text, current):

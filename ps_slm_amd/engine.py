@@ -22,12 +22,25 @@ projector is the FIRST layer of the network, so its gradients are the LAST thing
 hidden is the all-reduce of the final row block.  No other data-path collective exists.
 """
 import ctypes
+import json
+import logging
 import math
+import os
+import shutil
 
 import torch
 import torch.distributed as dist
 
 from .streams import side_stream
+
+logger = logging.getLogger(__name__)
+
+# ---- training state on disk (TasuEngine.save_state / load_state; DESIGN.md "Training state")
+STATE_FORMAT = 1
+STATE_CHUNK_ELEMS = 64 * 1024 * 1024       # fp32 elements per pass through the staging buffer (256 MB); tests lower it
+STATE_TENSORS = ("p", "m", "v")            # + "g_acc" with gradient_accumulation_steps > 1
+_SCHEDULE_KEYS = ("lr", "betas", "eps", "weight_decay", "warmup_num_steps", "total_num_steps", "warmup_min_ratio", "cos_min_ratio",
+                  "warmup_type")
 
 
 class RcclExchange:
@@ -167,6 +180,8 @@ class TasuEngine:
         # weight 1/k^2; the optimizer and the scheduler step on every k-th call of step().
         self.ga = max(1, int(ds_config.get("gradient_accumulation_steps", 1)))
         self._g_acc = torch.zeros_like(self.core.proj.g) if self.ga > 1 else None
+        self._stage = None             # save_state / load_state: the one staging buffer (pinned on the GPU), kept between saves
+        self._loaded_rng = None        # torch CPU generator state of the last load_state (restore_rng)
 
     # ---- nn.Module-like surface the reference's train() uses (deepspeed_utils.py:136-246)
     def train(self):
@@ -323,3 +338,186 @@ class TasuEngine:
             torch.save({k: v.cpu() for k, v in self.module.state_dict().items()}, path)          # the trainable tensors
         if self.world > 1:
             dist.barrier(group=self.pg)
+
+    # ---- training state: everything a run needs to CONTINUE (DeepSpeed's engine.save_checkpoint / load_checkpoint, which the
+    #      reference calls at checkpoint_handler.py:169-182 and declares the way back for at finetune_deepspeed.py:32-37).  The
+    #      weights-only file above stays what it is; this is the other half: AdamW moments, step counts, the accumulation window,
+    #      the dropout counter and the CPU generator.  Layout and reasons: DESIGN.md "Training state".
+    def state_fingerprint(self):
+        """What the flat bucket holds, in order: [checkpoint key, shape as stored, offset] of every tensor, plus what else decides
+        whether a saved bucket means the same thing in this model."""
+        from .full_ft import EMBED_KEY as FT_EMBED_KEY
+        core, pr = self.core, self.core.proj
+        entries = [["encoder_projector." + n, list(pr.offsets[n][1]), int(pr.offsets[n][0])] for n in pr.names]
+        if core.lora is not None:
+            for key, k in core.lora.names():
+                off, shp = core.lora.offsets[k]
+                entries.append([key, list(shp), int(off)])
+        if core.full_ft is not None:
+            ft = core.full_ft
+            for key, n, l, r0, nr in ft.names():
+                off, shp = ft.offsets[(n, l)]
+                row = 1
+                for d in shp[1:]:
+                    row *= int(d)
+                entries.append([key, [int(nr)] + [int(d) for d in shp[1:]], int(off) + int(r0) * row])
+        if core.embed_base is not None:
+            key = FT_EMBED_KEY if core.full_ft is not None else "llm.base_model.model.model.embed_tokens.weight"
+            entries.append([key, [core.geo.llm_vocab, core.geo.llm_dim], int(core.embed_base)])
+        return {"entries": entries, "trainable_lo": int(core.trainable_lo), "arith": core.arith_train, "projector": pr.kind}
+
+    def _state_tensors(self):
+        pr = self.core.proj
+        out = [(n, getattr(pr, n)) for n in STATE_TENSORS]
+        if self.ga > 1:
+            out.append(("g_acc", self._g_acc))
+        return out
+
+    def _staging(self, numel):
+        n = max(1, min(int(STATE_CHUNK_ELEMS), int(numel)))
+        if self._stage is None or self._stage.numel() != n:
+            self._stage = torch.empty(n, dtype=torch.float32, pin_memory=self.core.device.type == "cuda")
+        return self._stage
+
+    def _barrier(self):
+        if self.world > 1:
+            dist.barrier(group=self.pg)
+
+    def save_state(self, save_dir, tag=None, client_state=None):
+        """Writes ``<save_dir>/<tag>/`` (default tag ``global_step<N>``) and then points ``<save_dir>/latest`` at it; returns the
+        directory.  Call it between ``step()`` and the next forward.  The bucket's fp32 masters and moments (whole: frozen prefix
+        and alignment gaps included) go out as raw little-endian fp32 files in chunks of STATE_CHUNK_ELEMS through one staging
+        buffer -- never a host copy of the whole bucket.  The directory is built under a temporary name and renamed, ``latest`` is
+        replaced by a rename too: a save that dies half way never becomes ``latest``."""
+        if self._pending:
+            raise RuntimeError("save_state between backward() and step(): gradient ranges are still being exchanged")
+        tag = f"global_step{self.global_steps}" if tag is None else str(tag)
+        final, tmp = os.path.join(save_dir, tag), os.path.join(save_dir, tag + ".tmp")
+        if self.rank == 0:
+            os.makedirs(save_dir, exist_ok=True)
+            shutil.rmtree(tmp, ignore_errors=True)             # (left by an interrupted save of the same tag)
+            os.makedirs(tmp)
+        self._barrier()
+        lp = self.core.lora
+        torch.save({"lora_rng": lp.rng.detach().cpu() if lp is not None else None, "torch_rng": torch.get_rng_state(),
+                    "client_state": client_state}, os.path.join(tmp, f"rank_{self.rank}.pt"))
+        if self.rank == 0:
+            numel = int(self.core.proj.p.numel())
+            stage = self._staging(numel)
+            files = {}
+            for name, t in self._state_tensors():
+                with open(os.path.join(tmp, name + ".f32"), "wb") as f:
+                    for lo in range(0, numel, stage.numel()):
+                        k = min(stage.numel(), numel - lo)
+                        stage[:k].copy_(t[lo:lo + k])          # (device -> pinned host, ordered behind the step on this stream)
+                        f.write(memoryview(stage[:k].numpy()))
+                files[name + ".f32"] = numel * 4
+            meta = {"format": STATE_FORMAT, "global_steps": self.global_steps, "sched_iter": self.sched_iter,
+                    "micro_steps": self.micro_steps, "world": self.world, "numel": numel, "byteorder": "little",
+                    "gradient_accumulation_steps": self.ga, "files": files, "fingerprint": self.state_fingerprint(),
+                    "schedule": {k: self.cfg.get(k) for k in _SCHEDULE_KEYS}}
+            with open(os.path.join(tmp, "meta.json"), "w") as f:
+                json.dump(meta, f)
+        self._barrier()                                         # every rank's file is in place
+        if self.rank == 0:
+            shutil.rmtree(final, ignore_errors=True)
+            os.rename(tmp, final)
+            with open(os.path.join(save_dir, "latest.tmp"), "w") as f:
+                f.write(tag)
+            os.replace(os.path.join(save_dir, "latest.tmp"), os.path.join(save_dir, "latest"))
+        self._barrier()
+        return final
+
+    def load_state(self, load_dir, tag=None):
+        """-> (path, client_state), DeepSpeed's ``load_checkpoint`` convention; ``tag=None`` reads ``<load_dir>/latest``.  Everything
+        is validated before anything is overwritten (fingerprint, world size, file sizes); then the buffers are written IN PLACE --
+        captured hipGraphs and every view of the bucket stay valid -- and what derives from the masters is rebuilt by the calls an
+        optimizer step uses.  lr, betas and the schedule's lengths come from the current ds_config: the state carries positions."""
+        if tag is None:
+            latest = os.path.join(load_dir, "latest")
+            if not os.path.isfile(latest):
+                raise FileNotFoundError(f"no training state under {load_dir!r}: {latest} does not exist")
+            tag = open(latest).read().strip()
+        path = os.path.join(load_dir, str(tag))
+        meta_file = os.path.join(path, "meta.json")
+        if not os.path.isfile(meta_file):
+            raise FileNotFoundError(f"training state {path!r} does not exist (or is incomplete: no meta.json)")
+        meta = json.load(open(meta_file))
+        if meta.get("format") != STATE_FORMAT:
+            raise ValueError(f"{path}: state format {meta.get('format')!r}, this engine reads format {STATE_FORMAT}")
+        if int(meta["world"]) != self.world:
+            raise ValueError(f"{path}: saved at world size {meta['world']}, this run has {self.world} rank(s); resuming at another "
+                             "world size is not built")
+        mine, theirs = self.state_fingerprint(), meta["fingerprint"]
+        for i, (a, b) in enumerate(zip(mine["entries"], theirs["entries"])):
+            if a != b:
+                raise ValueError(f"{path}: the saved bucket differs from this model's at entry {i}: saved {b[0]!r} {b[1]} at offset "
+                                 f"{b[2]}, here {a[0]!r} {a[1]} at offset {a[2]}")
+        if len(mine["entries"]) != len(theirs["entries"]):
+            longer, who = (theirs, "the saved state") if len(theirs["entries"]) > len(mine["entries"]) else (mine, "this model")
+            e = longer["entries"][min(len(mine["entries"]), len(theirs["entries"]))]
+            raise ValueError(f"{path}: the saved bucket differs from this model's: only {who} holds {e[0]!r} {e[1]} at offset {e[2]}")
+        for k in ("trainable_lo", "arith", "projector"):
+            if mine[k] != theirs[k]:
+                raise ValueError(f"{path}: saved with {k}={theirs[k]!r}, this model has {k}={mine[k]!r}")
+        numel = int(self.core.proj.p.numel())
+        if int(meta["numel"]) != numel:
+            raise ValueError(f"{path}: the saved bucket has {meta['numel']} elements, this model's {numel}")
+        saved_ga = int(meta.get("gradient_accumulation_steps", 1))
+        mid_window = int(meta["micro_steps"]) % saved_ga != 0
+        if saved_ga != self.ga and mid_window:
+            raise ValueError(f"{path}: saved in the middle of an accumulation window of {saved_ga} micro-steps, this run accumulates {self.ga}")
+        names = [n for n, _ in self._state_tensors() if n != "g_acc" or saved_ga == self.ga]
+        for n in names:
+            fn = os.path.join(path, n + ".f32")
+            if not os.path.isfile(fn) or os.path.getsize(fn) != numel * 4 or meta["files"].get(n + ".f32") != numel * 4:
+                raise ValueError(f"{fn}: {os.path.getsize(fn) if os.path.isfile(fn) else 'no'} bytes on disk, meta.json records "
+                                 f"{meta['files'].get(n + '.f32')}, the bucket needs {numel * 4}")
+        rank_file = os.path.join(path, f"rank_{self.rank}.pt")
+        if not os.path.isfile(rank_file):
+            raise FileNotFoundError(f"{rank_file} does not exist")
+        mine_rank = torch.load(rank_file, map_location="cpu", weights_only=False)
+        lp = self.core.lora
+        if (lp is None) != (mine_rank["lora_rng"] is None):
+            raise ValueError(f"{rank_file}: LoRA dropout counter {'missing' if lp is not None else 'present'}")
+        for k, v in (meta.get("schedule") or {}).items():
+            cur = self.cfg.get(k)
+            if (list(cur) if isinstance(cur, (tuple, list)) else cur) != v:
+                logger.info("load_state: %s was %r when the state was saved, this run uses %r (the current ds_config holds)", k, v, cur)
+        if saved_ga != self.ga:
+            logger.info("load_state: gradient_accumulation_steps was %d, this run uses %d", saved_ga, self.ga)
+        # ---- nothing was touched so far; from here on the buffers are overwritten in place
+        stage = self._staging(numel)
+        tensors = dict(self._state_tensors())
+        for n in names:
+            t = tensors[n]
+            with open(os.path.join(path, n + ".f32"), "rb") as f:
+                for lo in range(0, numel, stage.numel()):
+                    k = min(stage.numel(), numel - lo)
+                    if f.readinto(memoryview(stage[:k].numpy()).cast("B")) != 4 * k:
+                        raise IOError(f"{path}/{n}.f32: short read")
+                    t[lo:lo + k].copy_(stage[:k])               # (synchronous: the staging buffer is free for the next chunk)
+        if self.ga > 1 and "g_acc" not in names:
+            self._g_acc.zero_()
+        if lp is not None:
+            lp.rng.copy_(mine_rank["lora_rng"])
+        self.global_steps, self.sched_iter = int(meta["global_steps"]), int(meta["sched_iter"])
+        self.micro_steps = int(meta["micro_steps"])
+        self._pending, self._last_state = [], None
+        # the bf16 image and every working copy (projector / adapter / decoder transposes, the embedding table's copies; the fp32
+        # and merged-adapter caches follow by their version counters): exactly what model.load_state_dict and step() call
+        self.core.sync_projector_copies()
+        if hasattr(self.module, "_masters_touched"):
+            self.module._masters_touched = False
+        self._loaded_rng = mine_rank["torch_rng"]
+        self.restore_rng()
+        self._barrier()
+        return path, mine_rank["client_state"]
+
+    load_checkpoint = load_state
+
+    def restore_rng(self):
+        """Sets the torch CPU generator (the CPS noise draws) to what the last ``load_state`` read.  ``load_state`` does it itself;
+        the training loop calls it once more after it has skipped the batches the saved run had consumed."""
+        if self._loaded_rng is not None:
+            torch.set_rng_state(self._loaded_rng)

@@ -259,7 +259,29 @@ def _inline_batches(dataset):
         yield raw, dataset.collator(raw)
 
 
-def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=None, metrics=None):
+def _split_rng(ds):
+    """The split's own ``random.Random`` (``main`` installs one per split), or None."""
+    inner = getattr(ds, "dp", ds)
+    rng = getattr(inner, "rng", None)
+    return rng if isinstance(rng, random.Random) else None
+
+
+def _prune_states(state_dir, keep=2):
+    """Keeps the ``keep`` newest complete ``global_step<N>`` states under ``state_dir`` (what ``latest`` names is among them);
+    directories of interrupted saves (``*.tmp``) and tags of another form are left alone."""
+    import re
+    import shutil
+    tags = []
+    for name in os.listdir(state_dir):
+        m = re.fullmatch(r"global_step(\d+)", name)
+        if m and os.path.isfile(os.path.join(state_dir, name, "meta.json")):
+            tags.append((int(m.group(1)), name))
+    for _, name in sorted(tags)[:-keep]:
+        shutil.rmtree(os.path.join(state_dir, name), ignore_errors=True)
+
+
+def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=None, metrics=None, resume=None, state_dir=None,
+          state_interval=0):
     """Loop body of Multitask/utils/deepspeed_utils.py:190-246 (uneven-data join, forward, backward, step, logging) and
     the validation / save-on-improvement block behind it (:248-290).
 
@@ -267,7 +289,19 @@ def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=N
     with the reader thread (BatchReader, the default) up to ``depth`` + 2 batches are in flight.  The prompt draws of those batches
     therefore come before the draws a validation pass at step i makes; ``main`` gives each split its own ``random.Random`` so that
     the two never share a stream (a fixed seed reproduces a run, with or without validation), but the draws are not those of the
-    reference's loop, whose DataLoader workers each own a forked copy of the global generator."""
+    reference's loop, whose DataLoader workers each own a forked copy of the global generator.
+
+    Training state (``state_dir``; ``state_interval`` optimizer steps, and wherever a validation improvement writes
+    ``pytorch_model.bin``): ``engine.save_state`` at the END of a loop iteration -- between ``engine.step()`` and the next forward; the
+    batches the loop holds ahead of the step are not part of the state.  Its ``client_state`` carries the loop's counters and
+    accumulators, the training split's generator as it was at the START of the epoch and the number of batches consumed since (the
+    reader runs ahead, so its current state says nothing), and the validation split's generator as it is (validation runs on this
+    thread).  ``resume`` = that ``client_state`` (from ``engine.load_state``): the split generators are put back, the reader or the
+    inline iterator starts the epoch again, the consumed batches are read, collated and DISCARDED -- resuming deep into an epoch
+    costs the reading (and, on the audio branch, the front end) of every skipped utterance once more; a cheaper skip is not built --
+    then the torch CPU generator is restored (last: collating must not disturb the CPS draws) and the loop continues.  The resumed
+    process has not announced its first batch to ``engine.prefetch``; that batch runs its encoder pass in line, results do not
+    change.  ``resume=None`` and no ``state_dir``: the loop as it always was."""
     results = {}
     total_loss, total_acc, steps, utts = 0.0, 0.0, 0, 0
     best_val_loss, best_val_acc = float("inf"), 0.0
@@ -280,13 +314,31 @@ def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=N
     metrics = metrics if metrics is not None else MetricsLog(log_config, rank)
     ga = max(1, int(getattr(engine, "ga", 1)))
     dynamic = train_config.batching_strategy == "dynamic"
-    for epoch in range(train_config.num_epochs):
+    train_rng, val_rng = _split_rng(dataset), _split_rng(eval_dataset)
+    first_epoch = 0
+    if resume is not None:
+        first_epoch, steps, utts = int(resume["epoch"]), int(resume["steps"]), int(resume["utts"])
+        total_loss, total_acc = resume["total_loss"], resume["total_acc"]
+        best_val_loss, best_val_acc = resume["best_val_loss"], resume["best_val_acc"]
+        val_loss, val_ppl, val_acc = list(resume["val_loss"]), list(resume["val_ppl"]), list(resume["val_acc"])
+        if train_rng is not None and resume["train_rng"] is not None:
+            train_rng.setstate(resume["train_rng"])
+        if val_rng is not None and resume["val_rng"] is not None:
+            val_rng.setstate(resume["val_rng"])
+    for epoch in range(first_epoch, train_config.num_epochs):
         engine.train()
         ep_loss, ep_acc, ep_n = 0.0, 0.0, 0
+        epoch_rng = train_rng.getstate() if train_rng is not None else None   # (before the reader starts drawing)
         reader = BatchReader(dataset, engine.core.device) if threaded else None
         it = iter(reader) if reader is not None else _inline_batches(dataset)
         epoch_step = 0                                         # the reference's `step + 1` (per epoch, :190, :248)
         e_t0, e_utts = time.perf_counter(), 0
+        if resume is not None:
+            epoch_step, ep_loss, ep_acc, ep_n = int(resume["epoch_step"]), resume["ep_loss"], resume["ep_acc"], int(resume["ep_n"])
+            for _ in range(int(resume["consumed"])):           # read, collated, dropped: see the docstring
+                next(it, None)
+            engine.restore_rng()
+            resume = None
         nxt, nxt_batch = next(it, (None, None))
         while True:
             raw, batch = nxt, nxt_batch
@@ -307,6 +359,8 @@ def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=N
             utts += batch["input_ids"].shape[0]
             e_utts += batch["input_ids"].shape[0]
             log_now = steps % max(1, log_config.log_interval) == 0
+            save_now = bool(state_dir) and state_interval > 0 and engine.global_steps % state_interval == 0 and \
+                engine.is_gradient_accumulation_boundary()
             if log_now and val_now:
                 # loss / acc are views into the step's result buffer, which the validation forwards below overwrite:
                 # read them first
@@ -320,6 +374,7 @@ def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=N
                     if rank == 0:
                         os.makedirs(d, exist_ok=True)
                     engine.save_checkpoint(os.path.join(d, "pytorch_model.bin"))
+                    save_now = save_now or bool(state_dir)     # the state that goes with these weights: at the end of this iteration
                 best_val_loss, best_val_acc = min(best_val_loss, el), max(best_val_acc, ea)
                 val_loss.append(el)
                 val_ppl.append(ppl)
@@ -336,6 +391,14 @@ def train(engine, dataset, train_config, log_config, rank, world, eval_dataset=N
                 if rank == 0:
                     logger.info("epoch %d step %d loss %.4f acc %.4f lr %.3e  %.1f utt/s", epoch + 1, steps, l, a,
                                 engine.get_lr()[0], world * utts / (time.perf_counter() - t0))
+            if save_now:
+                engine.save_state(state_dir, client_state=dict(
+                    epoch=epoch, epoch_step=epoch_step, consumed=epoch_step, steps=steps, utts=utts, total_loss=total_loss,
+                    total_acc=total_acc, ep_loss=ep_loss, ep_acc=ep_acc, ep_n=ep_n, best_val_loss=best_val_loss,
+                    best_val_acc=best_val_acc, val_loss=val_loss, val_ppl=val_ppl, val_acc=val_acc, train_rng=epoch_rng,
+                    val_rng=val_rng.getstate() if val_rng is not None else None))
+                if rank == 0:
+                    _prune_states(state_dir)
         if reader is not None:
             reader.close()
         if engine.core.device.type == "cuda":
@@ -398,8 +461,26 @@ def main(argv=None):
             inner.rng = random.Random(int(train_config.seed) * 1000003 + 7919 * rank + k)
     metrics = MetricsLog(log_config, rank, run_config={"train_config": vars(train_config), "model_config": vars(model_config),
                                                          "log_config": vars(log_config)})
+    # training state: deepspeed_ckpt_path is the directory of TasuEngine.save_state / load_state, deepspeed_ckpt_id a tag in it
+    # (default: what <path>/latest names).  Nothing there yet = a fresh start, so that the same command line can be launched again
+    # after an interruption
+    state_dir, state_tag, resume = cfg.get("deepspeed_ckpt_path", None), cfg.get("deepspeed_ckpt_id", None), None
+    state_interval = int(cfg.get("state_interval", 0) or 0)
+    if state_dir:
+        there = os.path.isdir(os.path.join(state_dir, str(state_tag))) if state_tag is not None else os.path.isfile(os.path.join(state_dir, "latest"))
+        if there:
+            path, resume = engine.load_state(state_dir, state_tag)
+            logger.info("resuming from %s: optimizer step %d", path, engine.global_steps)
+            if resume is None:
+                raise ValueError(f"{path} was not written by this training loop (no client_state): load it with engine.load_state")
+        else:
+            logger.info("deepspeed_ckpt_path=%s holds no %s: starting fresh", state_dir,
+                        "latest" if state_tag is None else f"state {state_tag!r}")
+    elif state_interval > 0 and train_config.output_dir and not str(train_config.output_dir).startswith("PATH/"):
+        state_dir = os.path.join(train_config.output_dir, "state")
     try:
-        results = train(engine, dataset, train_config, log_config, rank, world, eval_dataset, metrics=metrics)
+        results = train(engine, dataset, train_config, log_config, rank, world, eval_dataset, metrics=metrics, resume=resume,
+                        state_dir=state_dir, state_interval=state_interval)
     finally:
         metrics.finish()
     if rank == 0:

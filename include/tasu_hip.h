@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 20
+#define TASU_ABI_VERSION 21
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -583,6 +583,20 @@ int tasu_beam_update(const float* vals, const int32_t* idx, float* run_scores, f
                      int32_t* next_ids, int32_t* next_src, int32_t* next_pos, int32_t* next_slot, int32_t* next_lens,
                      int32_t* banned, int B, int n_beams, int max_new, int eos, int min_length, int S, int first,
                      void* stream);
+/* generate(repetition_penalty = p != 1): HF RepetitionPenaltyLogitsProcessor on the device decode loop (csrc/topk_hist.hip).
+ * tasu_beam_hist_update, after tasu_beam_update: hist [B * n_beams, max_new] (row stride max_new) becomes, per row m, the history
+ * of its parent row next_src[m] plus its new token next_ids[m], in place (one workgroup per utterance; parents are rows of the same
+ * utterance), and hist_len[m] = ctl[0]; a no-op once ctl[1] (done) is set.  max_new <= 2048, n_beams <= 5. */
+int tasu_beam_hist_update(int32_t* hist, int32_t* hist_len, const int32_t* ctl, const int32_t* next_src, const int32_t* next_ids,
+                          int B, int n_beams, int max_new, void* stream);
+/* tasu_logprob_topk with a per-row token history hist [M, hist_ld] of hist_len[m] (<= 2048) entries and the rule
+ * s' = s < 0 ? s * penalty : s / penalty, applied once per distinct history token.  mode 1 (HF greedy): on the raw logits, before the
+ * softmax.  mode 0 (HF beam search): on the log-probs, not renormalised.  A history token that is also banned scores -inf; a token
+ * appears at most once among the k outputs.  Same outputs, tie rule and workspace as tasu_logprob_topk; any k in 1..16;
+ * V <= 196608 (a column part lives in registers). */
+int tasu_logprob_topk_hist(const void* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, const int32_t* hist,
+                           int hist_ld, const int32_t* hist_len, float penalty, int mode, float* out_val, int32_t* out_idx,
+                           float* workspace, int64_t workspace_floats, void* stream);
 /* x[m,:] = table[ids[m],:] (fp32 embedding rows of the last generated tokens). */
 int tasu_embed_rows(const float* table, const int32_t* ids, float* x, int M, int D, void* stream);
 
@@ -791,6 +805,11 @@ int tasu_f32_attn_bwd(const float* qkv, const float* dout, const int32_t* kstart
  * with it the row is split over 16 workgroups + a merge launch (a decode step's 64 rows are too few workgroups for one per row).        */
 int tasu_f32_logprob_topk(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, float* out_val,
                           int32_t* out_idx, float* workspace, int64_t workspace_floats, void* stream);
+/* tasu_logprob_topk_hist on fp32 logits (the fp32 forms of exp / log and of the log-prob, (x - max) - log(sum)); always the 16-part
+ * split: the workspace of M * 16 * (2 + 2 k) floats is required, ld % 4 == 0, 16-byte aligned rows, V <= 163840. */
+int tasu_f32_logprob_topk_hist(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, const int32_t* hist,
+                               int hist_ld, const int32_t* hist_len, float penalty, int mode, float* out_val, int32_t* out_idx,
+                               float* workspace, int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------ decoder weight gradients
  * Full fine-tuning of the LLM (train_config.freeze_llm = false; Multitask/model/ps-slm.py:105-108 leaves every decoder parameter

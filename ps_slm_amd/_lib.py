@@ -109,6 +109,8 @@ PROTOTYPES = {
     "tasu_flac_info": [vp, i64, vp, vp],
     "tasu_flac_decode": [vp, i64, vp, i64, vp],
     "tasu_beam_update": [vp] * 21 + [i32] * 7 + [vp],
+    "tasu_beam_hist_update": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "tasu_logprob_topk_hist": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, i64, vp],
     "tasu_fbank": [vp, i64, f32, i32, i32, vp, vp, i32, f32, vp, vp],
     "tasu_lfr_cmvn": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "tasu_embed_rows": [vp, vp, vp, i32, i32, vp],
@@ -150,6 +152,7 @@ PROTOTYPES.update({
     "tasu_f32_swiglu": [vp, vp, i32, i32, vp],
     "tasu_f32_embed_merge": [vp, vp, i32, vp, vp, vp, i32, i32, vp],
     "tasu_f32_logprob_topk": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp],
+    "tasu_f32_logprob_topk_hist": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, i64, vp],
     "tasu_f32_ce": [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "tasu_f32_ca_attn": [vp, i32, vp, i32, i32, i32, f32, vp, i32, i32, vp, i64, vp],
     "tasu_f32_ca_workspace_floats": [i32, i32, i32, i32],
@@ -173,7 +176,7 @@ PROTOTYPES.update({
     "tasu_colsum_bf16_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

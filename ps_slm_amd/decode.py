@@ -12,6 +12,7 @@ KV append, cache attention, o GEMM + residual, RMSNorm, gate|up GEMM, SwiGLU, do
 GEMM -> log-softmax top-k -> beam update.  HBM-bound: every step streams the bf16 weights once.
 """
 import collections
+import logging
 
 import numpy as np
 import torch
@@ -20,6 +21,21 @@ from .model import HD, StepState, rup
 
 NEG = -1.0e9
 BEAM_MAX_NB, BEAM_MAX_B, DECODE_MAX_CTX = 5, 256, 2048   # limits of tasu_beam_update / tasu_decode_step_prologue / tasu_attn_decode
+log = logging.getLogger(__name__)
+_warned_prompt_not_penalised = False
+
+
+def check_repetition_penalty(penalty):
+    """HF RepetitionPenaltyLogitsProcessor's own check: a float > 0 (an int, a bool or None is refused like there)."""
+    if not isinstance(penalty, float) or not penalty > 0:
+        raise ValueError(f"`repetition_penalty` must be a strictly positive float, but is {penalty!r}")
+    return penalty
+
+
+def penalty_mode(num_beams):
+    """What HF hands RepetitionPenaltyLogitsProcessor: the raw logits in greedy search (num_beams = 1: mode 1), the log-softmax
+    output in ``_beam_search`` (mode 0, scores not renormalised afterwards).  Pinned by tests/golden/mid_generate_penalty.npz."""
+    return 1 if num_beams == 1 else 0
 
 
 class BeamState:
@@ -92,8 +108,9 @@ class BeamState:
 class DeviceBeam:
     """Device-resident beam-search state + the next step's inputs (the arguments of ``tasu_beam_update``)."""
 
-    def __init__(self, model, B, nb, max_new, eos, length_penalty, min_length, S, valid):
+    def __init__(self, model, B, nb, max_new, eos, length_penalty, min_length, S, valid, repetition_penalty=1.0):
         self.B, self.nb, self.max_new, self.eos, self.min_length, self.S = B, nb, max_new, int(eos), int(min_length), S
+        self.penalty = float(repetition_penalty)
         up, buf = model._upload, model._buf
         M = B * nb
         i32 = torch.int32
@@ -116,6 +133,12 @@ class DeviceBeam:
         self.next_ids, self.next_src = buf("in_dec_ids", (M,), i32), buf("in_dec_src", (M,), i32)
         self.next_pos, self.next_slot, self.next_lens = buf("in_dec_pos", (M,), i32), buf("in_dec_slot", (M,), i32), buf("in_dec_lens", (M,), i32)
         self.banned = up("dec_banned", np.array([eos if min_length > 0 else -1], dtype=np.int32))
+        self.hist = self.hist_len = None
+        if self.penalty != 1.0:
+            # generated tokens of every beam row (tasu_beam_hist_update keeps them next to the beam state): what HF's
+            # RepetitionPenaltyLogitsProcessor sees under inputs_embeds -- the prompt is not part of it
+            self.hist = buf("bm_hist", (M, max_new), i32)
+            self.hist_len = up("bm_hist_len", np.zeros(M, dtype=np.int32))
         self.done_host = None
         if model.device.type == "cuda":
             if getattr(model, "_done_host", None) is None:
@@ -156,7 +179,8 @@ def effective_min_length(min_length, S):
     return max(int(min_length) - int(S), 0)
 
 
-def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention):
+def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention,
+                  repetition_penalty=1.0):
     """Checks a generate() call against the limits of the device beam search (tasu_beam_update, tasu_decode_step_prologue:
     include/tasu_hip.h) and the context limit ``max_ctx`` of the caller's cache attention, BEFORE any prefill.  Returns
     (min_length in generated positions, eos, pad)."""
@@ -169,6 +193,15 @@ def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_toke
         raise ValueError("max_new_tokens must be >= 1")
     if S + max_new_tokens > max_ctx:
         raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds {attention} context limit {max_ctx}")
+    if check_repetition_penalty(repetition_penalty) != 1.0:
+        if not hasattr(model.ops, "beam_hist_update"):   # a missing kernel is an error, raised before any prefill work
+            raise NotImplementedError(f"generate(repetition_penalty={repetition_penalty!r}): the ops backend {type(model.ops).__name__} "
+                                      "has no token-history kernels (beam_hist_update, logprob_topk_hist)")
+        global _warned_prompt_not_penalised
+        if not _warned_prompt_not_penalised:          # HF's own sentence (generation/utils.py _get_logits_processor), once
+            _warned_prompt_not_penalised = True
+            log.warning("Passing `repetition_penalty` with `inputs_embeds` and without `input_ids` to `generate` will apply the penalty "
+                        "only to newly generated tokens, not to the prompt.")
     eos = model.geo.eos_id if eos_token_id is None else eos_token_id
     pad = eos if pad_token_id is None else pad_token_id
     return effective_min_length(min_length, S), eos, pad
@@ -198,6 +231,8 @@ def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
     if model.decode_graphs and model.device.type == "cuda":
         # hipGraph replay of device_step (~430 launches: ps_slm_amd/graphs.py), keyed by the scalars baked into its kernel arguments
         key = (tag, bs.B, bs.S, bs.nb, bs.S + bs.max_new, bs.max_new, bs.eos, bs.min_length)
+        if bs.penalty != 1.0:
+            key += (bs.penalty,)
         step = lambda: model._dec_graphs.run(key, device_step, lambda: model._buf_gen)
     if model.device.type == "cuda":
         # the host issues positions ahead of the device and looks at the pinned "done" word DONE_POLL_DEPTH positions late
@@ -220,7 +255,7 @@ def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
 
 
 def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
-                         eos_token_id=None, pad_token_id=None):
+                         eos_token_id=None, pad_token_id=None, repetition_penalty=1.0):
     """st: a prepared state whose projector output (st.dev['y2']) is ready.  Returns LongTensor [B, n_new] (CPU)."""
     if model.lora is not None and model._lora_run is not None:
         # use_peft: prefill and the decode loop run on the merged weights W + s B A (ps_slm_amd/lora.py: merged_llm)
@@ -228,12 +263,13 @@ def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, 
         keep = (model.llm, model._lora_run)
         model.llm, model._lora_run = merged_llm(model), None
         try:
-            return beam_search_generate(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos_token_id, pad_token_id)
+            return beam_search_generate(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos_token_id, pad_token_id,
+                                        repetition_penalty)
         finally:
             model.llm, model._lora_run = keep
     ops, geo = model.ops, model.geo
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, DECODE_MAX_CTX,
-                                         "the cache attention's")
+                                         "the cache attention's", repetition_penalty)
     # ---- prefill with the training-forward kernels (no loss)
     model.forward_llm(st, compute_loss=False, need_backward=False, logits_rows="none")
     # decode-step weights in the order the streaming kernels consume them (built once per model), and the decision whether the
@@ -241,7 +277,7 @@ def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, 
     model.llm.prepare_decode(ops)
     ops.begin_decode(geo.llm_dim, geo.llm_heads * HD, geo.llm_inter)
     try:
-        return _decode_after_prefill(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos, pad)
+        return _decode_after_prefill(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty)
     finally:
         ops.end_decode()
 
@@ -292,7 +328,7 @@ def layers_per_gemm(ops, geo, layers, final_norm, x, x2, xn, qkv, ao, act, cos, 
                 in_ssq[ci] = None
 
 
-def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_penalty, eos, pad):
+def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty=1.0):
     ops, geo, llm = model.ops, model.geo, model.llm
     B, S = st.B, st.S
     M, K = B * nb, 2 * nb
@@ -320,9 +356,21 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     ops.gemm(xn, llm.head, logits, B, V, D)
     tv = buf("dec_topv", (M, K), f32)
     ti = buf("dec_topi", (M, K), i32)
-    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid)
-    ops.logprob_topk(logits, B, V, K, bs.banned, 1, tv, ti)
-    ops.beam_update(tv, ti, bs, True)                                      # first position: only beam 0 exists
+    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty)
+    penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
+
+    def topk_and_update(rows, first):
+        """Per-row top-k and the beam update; under a repetition penalty the top-k reads every row's token history and the
+        history follows the beams after the update (``repetition_penalty == 1.0``: exactly the launches without the knob)."""
+        if penalised:
+            ops.logprob_topk_hist(logits, rows, V, K, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, pmode, tv, ti)
+        else:
+            ops.logprob_topk(logits, rows, V, K, bs.banned, 1, tv, ti)
+        ops.beam_update(tv, ti, bs, first)
+        if penalised:
+            ops.beam_hist_update(bs)
+
+    topk_and_update(B, True)                                               # first position: only beam 0 exists, empty history
     x = buf("dec_x", (M, D), f32)
     x2 = buf("dec_x2", (M, D), f32)
     qkv = buf("dec_qkv", (M, LDQ), bf)
@@ -346,8 +394,7 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
                         M, ctx, ws, normed=True)
         for m0, mc in chunks:
             ops.gemm_skinny(xn[m0:m0 + mc], llm.head, logits[m0:m0 + mc], mc, V, D, ws)
-        ops.logprob_topk(logits, M, V, K, bs.banned, 1, tv, ti)
-        ops.beam_update(tv, ti, bs, False)
+        topk_and_update(M, False)
 
     # the launch / layout switches decide which kernels device_step issues: a graph captured under one setting must not be
     # replayed under another (in-process A/B runs)

@@ -21,7 +21,7 @@ HBM-bound like the bf16 step, on twice the bytes: 6.2 GB of fp32 weights per gen
 import numpy as np
 import torch
 
-from .decode import DeviceBeam, decode_positions, generate_args, kv_row_index, prompt_rows
+from .decode import DeviceBeam, decode_positions, generate_args, kv_row_index, penalty_mode, prompt_rows
 from .model import HD, StepState, rup
 
 F32_MAX_CTX = 2048          # tasu_f32_attn_*: keys per query row
@@ -241,12 +241,12 @@ def forward_fp32(model, st: StepState, compute_loss=True):
 
 
 def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
-                              eos_token_id=None, pad_token_id=None):
+                              eos_token_id=None, pad_token_id=None, repetition_penalty=1.0):
     """st: a prepared state (prepare_text / prepare_audio).  Returns LongTensor [B, n_new] (CPU)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, F32_MAX_CTX,
-                                         "the fp32 attention's")
+                                         "the fp32 attention's", repetition_penalty)
     B, S, nb = st.B, st.S, num_beams
     ctx = S + max_new_tokens
     M, K = B * nb, 2 * nb
@@ -273,10 +273,21 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     ops.embed_rows(xn0, last_rows, xn, B, D)                    # the final-normed last prompt position of every utterance
     ops.f32_gemm(xn, weights_f32(model)["head"], logits, B, V, D, ws=ws)
     tv, ti = buf("dec_topv", (M, K), f32), buf("dec_topi", (M, K), i32)
-    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid)
+    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty)
     topk_ws = buf("f32_topk_ws", (M * 16 * (2 + 2 * K),), f32)               # the row split over 16 workgroups (tasu_f32_logprob_topk)
-    ops.f32_logprob_topk(logits, B, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
-    ops.beam_update(tv, ti, bs, True)
+    penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
+
+    def topk_and_update(rows, first):
+        """decode.py's topk_and_update on the fp32 logits (``repetition_penalty == 1.0``: exactly the launches without the knob)."""
+        if penalised:
+            ops.f32_logprob_topk_hist(logits, rows, V, K, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, pmode, tv, ti, ws=topk_ws)
+        else:
+            ops.f32_logprob_topk(logits, rows, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
+        ops.beam_update(tv, ti, bs, first)
+        if penalised:
+            ops.beam_hist_update(bs)
+
+    topk_and_update(B, True)                                                 # first position: empty history
     qkv, ao = buf("f32_qkv", (M, LDQ), f32), buf("f32_ao", (M, H * HD), f32)
     gu, act = buf("f32_gu", (M, 2 * I), f32), buf("f32_act", (M, I), f32)
     cos, sin = buf("dec_cos", (M, HD // 2), f32), buf("dec_sin", (M, HD // 2), f32)
@@ -295,7 +306,6 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
         for l in range(L):
             _layer_fp32(model, l, x, x, x, xn, qkv, ao, gu, act, M, cos, sin, attend_cache, ws, cache=(kcv[l], vcv[l], bs.next_slot), ctx=ctx, frag=frag)
         ops.f32_gemm(xn, head, logits, M, V, D, ws=ws)                                 # xn: the final norm, from the last layer's finisher
-        ops.f32_logprob_topk(logits, M, V, K, bs.banned, 1, tv, ti, ws=topk_ws)
-        ops.beam_update(tv, ti, bs, False)
+        topk_and_update(M, False)
 
     return decode_positions(model, bs, device_step, pad, "decode_fp32")

@@ -714,6 +714,20 @@ class HipOps:
                                              _p(out_idx), _p(self.topk_ws), self.topk_ws.numel(), self._stream()),
                   "tasu_logprob_topk")
 
+    def logprob_topk_hist(self, logits, M, V, k, banned, n_banned, hist, hist_len, penalty, mode, out_val, out_idx):
+        """logprob_topk under generate(repetition_penalty): ``hist`` [rows, max_new] int32 token history, ``hist_len`` [rows]
+        (tasu_logprob_topk_hist; mode 1: penalty on the raw logits -- greedy, mode 0: on the log-probs -- beam search)."""
+        if self.topk_ws.numel() < M * 16 * (2 + 2 * k):
+            raise TasuOpError(f"logprob_topk_hist: M={M}, k={k} exceeds the preallocated workspace")
+        self._chk(self.lib.tasu_logprob_topk_hist(_p(logits), logits.stride(0), M, V, k, _p(banned), n_banned, _p(hist), hist.stride(0),
+                                                  _p(hist_len), float(penalty), int(mode), _p(out_val), _p(out_idx), _p(self.topk_ws),
+                                                  self.topk_ws.numel(), self._stream()), "tasu_logprob_topk_hist")
+
+    def beam_hist_update(self, bs):
+        """Every beam row's token history after beam_update (tasu_beam_hist_update); ``bs``: ps_slm_amd.decode.DeviceBeam."""
+        self._chk(self.lib.tasu_beam_hist_update(_p(bs.hist), _p(bs.hist_len), _p(bs.ctl), _p(bs.next_src), _p(bs.next_ids), bs.B, bs.nb,
+                                                 bs.max_new, self._stream()), "tasu_beam_hist_update")
+
     def beam_update(self, vals, idx, bs, first):
         """One position of the device-side beam search (tasu_beam_update); ``bs``: ps_slm_amd.decode.DeviceBeam."""
         self._chk(self.lib.tasu_beam_update(_p(vals), _p(idx), _p(bs.run_scores), _p(bs.fin_scores), _p(bs.fin_len), _p(bs.fin_par),
@@ -867,6 +881,12 @@ class HipOps:
     def f32_attn_bwd(self, qkv, dout, kstart, dqkv, lse_ws, delta_ws, B, S, H, G, scale):
         self._chk(self.lib.tasu_f32_attn_bwd(_p(qkv), _p(dout), _p(kstart), _p(dqkv), _p(lse_ws), _p(delta_ws), B, S, H, G, scale,
                                              self._stream()), "tasu_f32_attn_bwd")
+
+    def f32_logprob_topk_hist(self, logits, M, V, k, banned, n_banned, hist, hist_len, penalty, mode, out_val, out_idx, ws):
+        """f32_logprob_topk under generate(repetition_penalty) (tasu_f32_logprob_topk_hist; the workspace is required)."""
+        self._chk(self.lib.tasu_f32_logprob_topk_hist(_p(logits), logits.stride(0), M, V, k, _p(banned), n_banned, _p(hist), hist.stride(0),
+                                                      _p(hist_len), float(penalty), int(mode), _p(out_val), _p(out_idx), _p(ws), ws.numel(),
+                                                      self._stream()), "tasu_f32_logprob_topk_hist")
 
     def f32_logprob_topk(self, logits, M, V, k, banned, n_banned, out_val, out_idx, ws=None):
         """``ws``: M * 16 * (2 + 2 k) floats -- with it the row is split over 16 workgroups (the decode step's 64 rows)."""

@@ -623,13 +623,15 @@ class slam_model_asr:
         from ps_slm_amd.decode import beam_search_generate
         core = self.core
         self._refresh_if_touched()
-        # the decode loop is HF beam search with do_sample=False (ps-slm.py:660-675 defaults): a sampling / penalty knob set to
-        # anything else would silently be ignored, so it is rejected
-        for name, default in (("do_sample", False), ("top_p", 1.0), ("repetition_penalty", 1.0), ("temperature", 1.0)):
+        # the decode loop is HF beam search with do_sample=False (ps-slm.py:660-675 defaults): a sampling knob set to anything else
+        # would silently be ignored, so it is rejected; repetition_penalty is served (ps_slm_amd/decode.py, HF's processor)
+        from ps_slm_amd.decode import check_repetition_penalty
+        repetition_penalty = check_repetition_penalty(kwargs.get("repetition_penalty", 1.0))
+        for name, default in (("do_sample", False), ("top_p", 1.0), ("temperature", 1.0)):
             if kwargs.get(name, default) != default:
                 raise NotImplementedError(f"generate({name}={kwargs[name]!r}): the MI355X decode loop implements the reference's "
                                           f"defaults only ({name}={default!r}, Multitask/model/ps-slm.py:660-675: beam search "
-                                          "without sampling, penalties or temperature)")
+                                          "without sampling or temperature)")
         if self.gt_emb:                                     # ps-slm.py:590-598
             texts = [re.sub(r"[^A-Za-z\s.,!?]+", "", t).lower().strip() for t in targets]
             ids_list = [self.encoder_tokenizer.encode(t) for t in texts]
@@ -645,4 +647,5 @@ class slam_model_asr:
                                     max_new_tokens=kwargs.get("max_new_tokens", 200),
                                     min_length=kwargs.get("min_length", 1),
                                     length_penalty=kwargs.get("length_penalty", 1.0),
+                                    repetition_penalty=repetition_penalty,
                                     eos_token_id=self.tokenizer.eos_token_id, pad_token_id=self.tokenizer.pad_token_id)

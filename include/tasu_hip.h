@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 21
+#define TASU_ABI_VERSION 22
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -839,6 +839,36 @@ int tasu_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, float* C, 
 int tasu_rmsnorm_wgrad(const void* dy_bf16, const float* x, const float* rstd, const int32_t* src_rows, float* dw, float* ws, int R, int D,
                        int accumulate, void* stream);
 int tasu_colsum_bf16_split(const void* x, int ld, float* out, float* ws, int R, int C, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------ decoder weight gradients, fp32 step
+ * Full fine-tuning of the LLM under the reference's own arithmetic (train_config.freeze_llm = false with use_fp16 = false: the
+ * dataclass defaults, aispeech_asr_config.py:89,116; Multitask/model/ps-slm.py:105-108 leaves every decoder parameter trainable and
+ * Multitask/utils/deepspeed_utils.py:205-236 runs loss.backward() outside autocast, so torch's Linear / Qwen2RMSNorm backward forms
+ * every weight gradient in fp32).  csrc/wgrad_f32.hip.
+ * tasu_f32_gemm_tn: C[N, K] (fp32, leading dimension ldc) = (accumulate == 0) or += sum_r A[r, n] . B[r, k] -- nn.Linear's
+ * dW = dY^T X with A = dY [R, N] and B = X [R, K], both fp32 and ROW-major as the fp32 step leaves them: the token rows are the
+ * reduction and no transposed copy is made (v_mfma_f32_16x16x4_f32 reads sixteen floats of one reduction row per operand: both
+ * fragments come straight out of row-major LDS tiles; 128 x 128 tiles, stages of 16 rows).  nsplit > 1 cuts the rows into that many
+ * ranges of whole 16-row stages, one fp32 slab [N, K] each in ws, summed in ascending slab order by a second launch (deterministic;
+ * for outputs with too few tiles to fill the chip: tasu_f32_gemm_tn_split gives the count to use, host code, -1 on bad sizes).
+ * Rules (anything else: TASU_ERR_ARG before any launch): R >= 1 (any); N % 4 == 0 and K % 4 == 0; lda >= N, ldb >= K, ldc >= K, all
+ * % 4 == 0; A, B, C (and ws) 16-byte aligned; 1 <= nsplit <= min(TASU_F32_GEMM_TN_MAX_SPLIT, ceil(R / 16)); nsplit > 1 needs
+ * ws_floats >= nsplit * N * K.  Elements of C outside [N, K] are never written; rows >= R of A / B are never read.
+ * tasu_f32_rmsnorm_wgrad: dw[j] = or += sum_r dy[r, j] . x[r, j] . rstd[r] -- the weight gradient of Qwen2RMSNorm
+ * (modeling_qwen2.py:41-48 differentiated) from the fp32 dy and x tasu_f32_rmsnorm_bwd reads.  rstd: [R] floats, or NULL: recomputed
+ * from x and eps (sum of squares in double) into the R floats behind the slabs of ws.  Two stages (TASU_RMS_WGRAD_SPLIT interleaved
+ * row slabs into ws, then their sum in slab order): deterministic.  ws_floats >= TASU_RMS_WGRAD_SPLIT * D (+ R without rstd);
+ * D % 4 == 0; dy, x, ws 16-byte aligned.
+ * tasu_f32_colsum_split: out[c] = or += sum_r x[r, c] of an fp32 [R, C] matrix (leading dimension ld) by the same two stages -- the
+ * q|k|v bias gradient (nn.Linear's db = column sums of dY) over thousands of token rows, where tasu_f32_colsum's one thread per
+ * column walks all rows alone.  ws: TASU_RMS_WGRAD_SPLIT * C floats; C % 4 == 0, ld % 4 == 0, ld >= C; x, ws 16-byte aligned.      */
+#define TASU_F32_GEMM_TN_MAX_SPLIT 16
+int tasu_f32_gemm_tn_split(int R, int N, int K);
+int tasu_f32_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int R, int N, int K, int accumulate, int nsplit,
+                     float* ws, int64_t ws_floats, void* stream);
+int tasu_f32_rmsnorm_wgrad(const float* dy, const float* x, const float* rstd, float* dw, float* ws, int64_t ws_floats, int R, int D,
+                           float eps, int accumulate, void* stream);
+int tasu_f32_colsum_split(const float* x, int ld, float* out, float* ws, int R, int C, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------ FLAC (host)
  * The reference reads ``.flac`` entries with torchaudio.load (speech_dataset_large.py:123-127: [C, T] float

@@ -174,9 +174,14 @@ PROTOTYPES.update({
     "tasu_gemm_tn_bf16": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp],
     "tasu_rmsnorm_wgrad": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "tasu_colsum_bf16_split": [vp, i32, vp, vp, i32, i32, i32, vp],
+    # ... and on the fp32 step (csrc/wgrad_f32.hip)
+    "tasu_f32_gemm_tn_split": [i32, i32, i32],
+    "tasu_f32_gemm_tn": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp],
+    "tasu_f32_rmsnorm_wgrad": [vp, vp, vp, vp, vp, i64, i32, i32, f32, i32, vp],
+    "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

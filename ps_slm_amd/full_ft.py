@@ -18,7 +18,14 @@ transpose, the fragment-order decode copies and the decode graphs -- follows eve
 Weight gradients (fp32, straight into the bucket): dW = dY^T X by tasu_gemm_tn_bf16 from the row-major bf16 operands the step keeps
 (the normed inputs, the attention output, the SwiGLU output: per layer in this mode), the q|k|v bias by tasu_colsum_bf16_split of dqkv
 behind the RoPE backward, the norm weights by tasu_rmsnorm_wgrad from exactly what tasu_rmsnorm_bwd reads.  On the main stream,
-next to the dgrad that consumes the same dY."""
+next to the dgrad that consumes the same dY.
+
+On the fp32 training step (``arith_train == "fp32"``: use_fp16 = false) the bucket layout is the same, and the masters ARE the weights:
+``llm.f32["layers"][l][wqkv | bqkv | wo | wgu | wd]`` and the untied ``llm.f32["head"]`` become views of ``p`` (the separately allocated
+fp32 copies are released; the bf16 views of ``pb`` stay, AdamW keeps writing the image), the weight gradients come from the fp32
+operands of ps_slm_amd/train_fp32.py by csrc/wgrad_f32.hip (``wgrad32`` -- per tensor on the faster of tasu_f32_gemm_tn and the composed
+route --, ``bias_wgrad32``, ``norm_wgrad32``), and after a step the
+fp32 transposed copies of the dgrads are redone in place and the fp32 fragment-order decode copies dropped."""
 import numpy as np
 import torch
 
@@ -44,9 +51,15 @@ class LLMTrainables:
         geo, pr = model.geo, model.proj
         self.model, self.geo = model, geo
         self.tn_min_split = 3                                # wgrad(): tasu_gemm_tn_bf16 from this many row ranges on (tests: 1 / 99 force a route)
+        # wgrad32(): the route of every fused tensor's weight gradient on the fp32 step, the faster one measured per shape at
+        # Qwen2.5-1.5B (other geometries: not measured, the same map); f32_route = "tn" / "composed" forces one (tests)
+        self.f32_routes = {"wqkv": "composed", "wo": "tn", "wgu": "tn", "wd": "composed", "head": "tn"}
+        self.f32_route = None
         D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
         if D % 8 or I % 8:
             raise NotImplementedError(f"freeze_llm=false: llm_dim {D} / intermediate_size {I} must be multiples of 8 (tasu_gemm_tn_bf16)")
+        if self.fp32 and V % 4:
+            raise NotImplementedError(f"freeze_llm=false on the fp32 step: vocabulary size {V} must be a multiple of 4 (tasu_f32_gemm_tn)")
         Q, KV = H * HD, G * HD
         self.shapes = {"wd": (D, I), "wgu": (2 * I, D), "ln2": (D,), "wo": (D, Q), "wqkv": (Q + 2 * KV, D), "bqkv": (Q + 2 * KV,), "ln1": (D,)}
         # reference module name -> (fused tensor, first row, rows)
@@ -78,6 +91,11 @@ class LLMTrainables:
             self.layer_range[l] = (lo, off)
         self.end = off
         pr.extend(self.end - pr.numel)
+
+    @property
+    def fp32(self):
+        """The decoder trains on the fp32 step: the forward reads the fp32 masters themselves."""
+        return self.model.arith_train == "fp32"
 
     # ---- views
     def view(self, flat, name, layer=None):
@@ -116,6 +134,7 @@ class LLMTrainables:
         m = self.model
         llm, pr, dev = m.llm, m.proj, m.device
         f = lambda t: t.to(dev, torch.float32)
+        f32w = llm.f32 if self.fp32 and llm.f32 else None              # fp32 step: masters from (and then instead of) the fp32 copies
         for l, w in enumerate(llm.layers):
             if sd is not None:
                 for mod, (n, r0, nr) in self.parts.items():
@@ -123,12 +142,17 @@ class LLMTrainables:
             else:
                 for n in LAYER_ORDER:
                     if w[n].data_ptr() != self.view(pr.p if n in F32_TENSORS else pr.pb, n, l).data_ptr():
-                        self.view(pr.p, n, l).copy_(f(w[n]))
+                        src = f32w["layers"][l].get(n, w[n]) if f32w is not None else w[n]
+                        if src.data_ptr() != self.view(pr.p, n, l).data_ptr():
+                            self.view(pr.p, n, l).copy_(f(src))
             for n in LAYER_ORDER:
                 new = self.view(pr.p if n in F32_TENSORS else pr.pb, n, l)
                 if n in ("wqkv", "wo", "wgu", "wd") and w[n].data_ptr() != new.data_ptr():
                     llm._stale_ptrs.append(w[n].data_ptr())          # its fragment-order decode copy dies with it
                 w[n] = new
+            if f32w is not None:
+                for n in ("wqkv", "bqkv", "wo", "wgu", "wd"):
+                    f32w["layers"][l][n] = self.view(pr.p, n, l)
         norm = self.view(pr.p, "norm")
         if sd is not None:
             norm.copy_(f(sd[NORM_KEY]))
@@ -140,9 +164,16 @@ class LLMTrainables:
             if sd is not None:
                 self.view(pr.p, "head").copy_(f(sd.get(HEAD_KEY, sd[EMBED_KEY])))
             elif llm.head.data_ptr() != head.data_ptr():
-                self.view(pr.p, "head").copy_(f(llm.head))
+                src = f32w["head"] if f32w is not None and f32w.get("head") is not None else llm.head
+                if src.data_ptr() != self.view(pr.p, "head").data_ptr():
+                    self.view(pr.p, "head").copy_(f(src))
                 llm._stale_ptrs.append(llm.head.data_ptr())
             llm.head = head
+            if f32w is not None:
+                f32w["head"] = self.view(pr.p, "head")
+        if f32w is not None:                                            # copies derived from the replaced fp32 tensors
+            for k in ("t", "frag", "frag_head"):
+                f32w.pop(k, None)
         llm._decode_ready = False
         m._graphs.clear()
         m._dec_graphs.clear()
@@ -180,6 +211,20 @@ class LLMTrainables:
             ops.forget_decode_weights(ptrs)
         llm._decode_ready = False
         m._dec_graphs.clear()
+        if self.fp32 and llm.f32:
+            # the fp32 paths: the dgrads' transposed copies follow in place (tasu_f32_transpose; the tied head's in _embed_changed);
+            # the fragment-order decode copies are dropped and made again by the next generate()
+            t = llm.f32.get("t")
+            if t is not None:
+                for f, ft in zip(llm.f32["layers"], t["layers"]):
+                    for n in ("wqkv", "wo", "wgu", "wd"):
+                        N, K = f[n].shape
+                        ops.f32_transpose(f[n], ft[n], N, K, N)
+                if not geo.tied and t.get("head") is not None:
+                    ops.f32_transpose(llm.f32["head"], t["head"], geo.llm_vocab, geo.llm_dim, t["head"].shape[1])
+            llm.f32.pop("frag", None)
+            if not geo.tied:
+                llm.f32.pop("frag_head", None)
 
     # ---- the backward's weight-gradient calls
     def wgrad(self, dy, x, name, layer):
@@ -217,3 +262,47 @@ class LLMTrainables:
         m = self.model
         ws = m._buf("wgrad_rms_ws", (RMS_WGRAD_SPLIT * self.geo.llm_dim,), torch.float32)
         m.ops.rmsnorm_wgrad(dy, x, rstd, self.view(m.proj.g, name, layer), ws, src_rows=src_rows, accumulate=False)
+
+    # ---- ... on the fp32 step (ps_slm_amd/train_fp32.py backward_fp32)
+    def wgrad32(self, dy, x, name, layer=None, dst=None):
+        """g[name] [N, K] = dy^T x from the fp32 operands (overwriting) on the route ``f32_routes`` keeps for it; ``dst``: another
+        destination of the same shape (the tied table's range for the head term).  See ``f32_wgrad``."""
+        f32_wgrad(self.model, dy, x, self.view(self.model.proj.g, name, layer) if dst is None else dst, self.f32_route or self.f32_routes[name])
+
+    def bias_wgrad32(self, dy, name, layer):
+        from .ops import RMS_WGRAD_SPLIT
+        m = self.model
+        R, C = dy.shape
+        ws = m._buf("f32t_wgrad_bias_ws", (RMS_WGRAD_SPLIT * C,), torch.float32)
+        m.ops.f32_colsum_split(dy, self.view(m.proj.g, name, layer), ws, R, C)
+
+    def norm_wgrad32(self, dy, x, name, layer):
+        """g[name] = sum_r dy . x . rstd with rstd recomputed from x, as tasu_f32_rmsnorm_bwd does."""
+        from .ops import RMS_WGRAD_SPLIT
+        m = self.model
+        R, D = dy.shape
+        ws = m._buf("f32t_wgrad_rms_ws", (RMS_WGRAD_SPLIT * D + rup(R, 4),), torch.float32)
+        m.ops.f32_rmsnorm_wgrad(dy, x, self.view(m.proj.g, name, layer), ws, self.geo.rms_eps)
+
+
+def f32_wgrad(model, dy, x, dst, route="tn"):
+    """dst [N, K] (fp32, overwriting) = dy[:, :N]^T x[:, :K] over all rows of the fp32 operands.  Two routes (DESIGN.md 4l has the
+    measured times): "tn" = tasu_f32_gemm_tn on the row-major operands, cut into the row ranges its split plan gives; "composed" =
+    the route the projector's weight gradients take -- two tasu_f32_transpose (rows zero-padded to 32, the NT GEMM's K granule) +
+    tasu_f32_gemm_nt."""
+    from .decode_fp32 import _gemm_ws
+    ops = model.ops
+    R = dy.shape[0]
+    N, K = dst.shape
+    if route == "tn":
+        ns = ops.f32_gemm_tn_split(R, N, K)
+        ws = model._buf("f32t_wgrad_tn_ws", (ns * N * K,), torch.float32) if ns > 1 else None
+        return ops.f32_gemm_tn(dy, x, dst, R, N, K, accumulate=False, nsplit=ns, ws=ws)
+    if route != "composed":
+        raise ValueError(f"f32_wgrad: unknown route {route!r}")
+    Rp = rup(R, 32)
+    dy_t = model._buf("f32t_wgrad_dy_t", (N, Rp), torch.float32)
+    x_t = model._buf("f32t_wgrad_x_t", (K, Rp), torch.float32)
+    ops.f32_transpose(dy, dy_t, R, N, Rp)
+    ops.f32_transpose(x, x_t, R, K, Rp)
+    ops.f32_gemm(dy_t, x_t, dst, N, K, Rp, ws=_gemm_ws(model))

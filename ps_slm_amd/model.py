@@ -591,9 +591,10 @@ class TasuModel:
             raise RuntimeError("the LLM is already trainable on this model")
         if self.lora is not None or self.embed_base is not None:
             raise RuntimeError("enable_llm_training with LoRA / use_emb: freeze_llm=false with use_peft=true is the LoRA recipe (peft freezes the base weights)")
-        if self.arith_train == "fp32":
-            raise NotImplementedError("freeze_llm=false on the fp32 training step: ps_slm_amd/train_fp32.py has no weight gradients of the "
-                                      "decoder (full fine-tuning runs on the bf16-autocast step: use_fp16=true)")
+        if self.arith_train == "fp32" and not self.f32_wgrad_served:
+            raise NotImplementedError("freeze_llm=false on the fp32 training step: the decoder's fp32 weight gradients (csrc/wgrad_f32.hip) "
+                                      "need the GPU operators; on this device / operator set full fine-tuning runs on the bf16-autocast "
+                                      "step: use_fp16=true")
         ft = LLMTrainables(self)
         self.enable_embedding_training()                   # [.. | embedding table]: lookup term + the tied head's term, as with use_emb
         self.full_ft = ft
@@ -635,9 +636,12 @@ class TasuModel:
         Call after enable_lora and before an engine is built on the model (the bucket grows)."""
         if self.embed_base is not None:
             raise RuntimeError("the embedding table is already trainable on this model")
-        if self.arith_train == "fp32":
-            raise NotImplementedError("use_emb on the fp32 training step: ps_slm_amd/train_fp32.py has no backward into the embedding "
-                                      "table (the table trains on the bf16-autocast step)")
+        if self.arith_train == "fp32" and not self.f32_wgrad_served:
+            raise NotImplementedError("use_emb on the fp32 training step: the backward into the embedding table needs the GPU's fp32 "
+                                      "operators (csrc/wgrad_f32.hip); on this device / operator set the table trains on the bf16-autocast "
+                                      "step (use_fp16=true)")
+        if self.arith_train == "fp32" and self.geo.tied and self.geo.llm_vocab % 4:
+            raise NotImplementedError(f"use_emb on the fp32 step: vocabulary size {self.geo.llm_vocab} must be a multiple of 4 (tasu_f32_gemm_tn)")
         pr, geo = self.proj, self.geo
         if geo.llm_dim % 4:
             raise NotImplementedError(f"use_emb: llm_dim {geo.llm_dim} is not a multiple of 4 (16-byte rows of the table's gradient)")
@@ -645,6 +649,11 @@ class TasuModel:
         pr.extend(base - pr.numel + geo.llm_vocab * geo.llm_dim)
         self.embed_base = base
         self._adopt_embed()
+
+    @property
+    def f32_wgrad_served(self):
+        """Whether the fp32 step can form gradients of the decoder's tensors / the embedding table: a GPU and its fp32 operators."""
+        return self.device.type != "cpu" and all(hasattr(self.ops, n) for n in ("f32_gemm_tn", "f32_rmsnorm_wgrad", "f32_colsum_split", "embed_bwd"))
 
     @property
     def proj_end(self):
@@ -736,7 +745,11 @@ class TasuModel:
                     f.pop("frag_head", None)
                     for k in ("frag", "t"):
                         if f.get(k) is not None:
-                            f[k]["head"] = None
+                            ht = f[k].get("head")
+                            if k == "t" and ht is not None and self.embed_base is not None and self.arith_train == "fp32" and hasattr(ops, "f32_transpose"):
+                                ops.f32_transpose(llm.embed, ht, V, D, ht.shape[1])   # a table that trains on the fp32 step: redone in place, every step
+                            else:
+                                f[k]["head"] = None
         elif getattr(llm, "_ca_e", None) is not None:
             if self.embed_base is None:
                 ops.cast_bf16(llm.embed, llm._ca_e)

@@ -344,6 +344,32 @@ class HipOps:
         self._chk(self.lib.tasu_colsum_bf16_split(_p(x), x.stride(0), _p(out), _p(ws), R, Cn, int(accumulate), self._stream()),
                   "tasu_colsum_bf16_split")
 
+    # ------------------------------------------------------------------ ... on the fp32 step (csrc/wgrad_f32.hip)
+    def f32_gemm_tn_split(self, R, N, K):
+        """How many row ranges f32_gemm_tn should cut R into for this output (host code): the caller sizes ``ws`` with it."""
+        return int(self.lib.tasu_f32_gemm_tn_split(R, N, K))
+
+    def f32_gemm_tn(self, a, b, c, R, N, K, accumulate=False, nsplit=1, ws=None):
+        """c[N, K] (fp32) = or += a[:R, :N]^T @ b[:R, :K]: a Linear's weight gradient dW = dY^T X from the row-major fp32 tensors
+        of the fp32 step, no transposed copies.  ``nsplit`` > 1: that many row ranges, fp32 slabs in ``ws`` (nsplit * N * K floats),
+        summed in slab order."""
+        self._chk(self.lib.tasu_f32_gemm_tn(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0), R, N, K, int(accumulate),
+                                            int(nsplit), _p(ws), 0 if ws is None else ws.numel(), self._stream()), "tasu_f32_gemm_tn")
+
+    def f32_rmsnorm_wgrad(self, dy, x, dw, ws, eps, rstd=None, accumulate=False):
+        """dw[j] = or += sum_r dy[r, j] * x[r, j] * rstd[r]: the RMSNorm weight gradient from what f32_rmsnorm_bwd reads; ``rstd``
+        None: recomputed from x and eps.  ``ws``: RMS_WGRAD_SPLIT * D floats (+ R without rstd)."""
+        R, D = dy.shape
+        self._chk(self.lib.tasu_f32_rmsnorm_wgrad(_p(dy), _p(x), _p(rstd), _p(dw), _p(ws), ws.numel(), R, D, float(eps), int(accumulate),
+                                                  self._stream()), "tasu_f32_rmsnorm_wgrad")
+
+    def f32_colsum_split(self, x, out, ws, R, Cn, accumulate=False):
+        """out[:Cn] = or += column sums of the fp32 x[:R, :Cn] in two stages (``ws``: RMS_WGRAD_SPLIT * Cn floats)."""
+        if ws.numel() < RMS_WGRAD_SPLIT * Cn:
+            raise TasuOpError(f"f32_colsum_split: workspace of {ws.numel()} floats, {RMS_WGRAD_SPLIT * Cn} needed")
+        self._chk(self.lib.tasu_f32_colsum_split(_p(x), x.stride(0), _p(out), _p(ws), R, Cn, int(accumulate), self._stream()),
+                  "tasu_f32_colsum_split")
+
     # ------------------------------------------------------------------ rope + attention
     def rope_table(self, pos, cos, sin, head_dim, theta):
         self._chk(self.lib.tasu_rope_table(_p(pos), _p(cos), _p(sin), pos.numel(), head_dim, theta, self._stream()),

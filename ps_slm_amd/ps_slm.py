@@ -210,16 +210,31 @@ def model_factory(train_config, model_config, **kwargs):
                                   "'cross-attention' (EncoderProjectorCTCCA, :104-126); q-former / simple_linear are not built")
     # train_config.freeze_llm = false (the dataclass default, aispeech_asr_config.py:116): setup_llm leaves every decoder parameter
     # trainable (ps-slm.py:105-108).  With use_peft=true peft freezes the base weights itself (the knob's help text says so): the LoRA
-    # recipe, as with freeze_llm=true.  Without it the whole decoder trains (ps_slm_amd/full_ft.py), on the bf16-autocast step only
+    # recipe, as with freeze_llm=true.  Without it the whole decoder trains (ps_slm_amd/full_ft.py): on the bf16-autocast step with
+    # use_fp16=true, on the fp32 step (csrc/wgrad_f32.hip) with use_fp16=false wherever the model's training arithmetic is fp32
     full_ft = not train_config.get("freeze_llm", True)
     if full_ft and train_config.get("use_peft", False):
         logger.warning("train_config.freeze_llm is false with use_peft=true: peft freezes the base weights itself -- the LoRA recipe, "
                        "exactly what freeze_llm=true builds")
         full_ft = False
+    # the fp32 kernels run on the GPU only: device "cpu" / an operator set without the f32_* weight-gradient operators has none
+    device = kwargs.get("device", None)
+    if device is None:
+        device = f"cuda:{int(os.environ.get('LOCAL_RANK', train_config.get('device', 0) or 0))}"
+    f32_wgrads = not str(device).startswith("cpu") and (kwargs.get("ops", None) is None or hasattr(kwargs["ops"], "f32_gemm_tn"))
     if full_ft and not train_config.get("use_fp16", False):
-        raise NotImplementedError("train_config.freeze_llm=false with use_fp16=false: the fp32 training step has no weight gradients of "
-                                  "the decoder; full fine-tuning of the LLM runs on the bf16-autocast step -- set use_fp16=true (or "
-                                  "freeze_llm=true: Multitask/scripts/finetune_deespeed_sensevoice.sh:84)")
+        if not f32_wgrads:
+            raise NotImplementedError("train_config.freeze_llm=false with use_fp16=false: the decoder's fp32 weight gradients need the GPU's "
+                                      "fp32 operators, which this device / operator set does not have; there full fine-tuning of the LLM "
+                                      "runs on the bf16-autocast step -- set use_fp16=true (or freeze_llm=true: "
+                                      "Multitask/scripts/finetune_deespeed_sensevoice.sh:84)")
+        if not train_config.get("ctc_posterior", True):
+            raise NotImplementedError("train_config.freeze_llm=false with use_fp16=false on raw encoder features (ctc_posterior=false): the "
+                                      "fp32 step's decoder weight gradients serve the CTC-posterior branch; set use_fp16=true")
+        if projector != "linear-silu" and train_config.get("mixed_precision", True):
+            raise NotImplementedError(f"train_config.freeze_llm=false with use_fp16=false and mixed_precision=true on the {projector} "
+                                      "projector: the model would train on the bf16 step and evaluate in fp32 -- set mixed_precision=false "
+                                      "(fp32 everywhere: the decoder trains on the fp32 step) or use_fp16=true")
     if train_config.get("quantization", False):
         raise NotImplementedError("train_config.quantization (ps-slm.py:101-102: bitsandbytes 8-bit weights) is not built")
     if kwargs.get("peft_ckpt", None):
@@ -244,10 +259,10 @@ def model_factory(train_config, model_config, **kwargs):
         logger.warning("train_config.use_emb is true but use_peft is false: the reference only looks at use_emb inside its use_peft "
                        "branch (ps-slm.py:114-123) and ignores it here -- the embedding table stays frozen")
         use_emb = False
-    if use_emb and no_bf16:
-        raise NotImplementedError("train_config.use_emb with use_fp16=false and mixed_precision=false: the fp32 training step has no "
-                                  "backward into the embedding table; use_emb trains on the bf16-autocast step (use_fp16=true, or "
-                                  "mixed_precision=true)")
+    if use_emb and no_bf16 and not f32_wgrads:
+        raise NotImplementedError("train_config.use_emb with use_fp16=false and mixed_precision=false: the fp32 step's backward into the "
+                                  "embedding table needs the GPU's fp32 operators, which this device / operator set does not have; there "
+                                  "use_emb trains on the bf16-autocast step (use_fp16=true, or mixed_precision=true)")
     if no_bf16 and not f32_train_served:
         what = f"{projector} projector" + (" with LoRA adapters" if use_peft else "") + (" on raw encoder features" if raw else "")
         if raw:
@@ -283,9 +298,6 @@ def model_factory(train_config, model_config, **kwargs):
     tokenizer = setup_tokenizer(train_config, model_config, geo, **kwargs)
     if not isinstance(tokenizer, SyntheticLLMTokenizer):
         geo.speech_id, geo.eos_id = tokenizer.default_speech_token, tokenizer.eos_token_id
-    device = kwargs.get("device", None)
-    if device is None:
-        device = f"cuda:{int(os.environ.get('LOCAL_RANK', train_config.get('device', 0) or 0))}"
     ops = kwargs.get("ops", None)
     if ops is None:
         from ps_slm_amd.ops import HipOps     # raises if libtasu_hip.so is missing or there is no GPU: no fallback

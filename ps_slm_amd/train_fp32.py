@@ -12,8 +12,11 @@ Multitask/scripts/finetune_deespeed_sensevoice.sh:37 -- forward and backward out
             gradients straight into the flat fp32 bucket ``proj.g`` (what TasuEngine's AdamW and the autograd boundary read).
 
 A correctness mode: ~10x slower than the bf16 step at Qwen2.5-1.5B (271 against 28 ms per 16 utterances: the fp32 matrix rate is 1/16 of bf16's; the step runs at 0.61 of it); pinned on the
-real reference's fp32 goldens (loss within 2e-5, projector gradients within 2e-4 relative L2: tests/test_gpu_model.py).  Decoder weights stay
-frozen (dgrad only), like the bf16 step.  Every projector the package serves trains here -- linear-silu, linear and cov1d-linear
+real reference's fp32 goldens (loss within 2e-5, projector gradients within 2e-4 relative L2: tests/test_gpu_model.py).  By default the
+decoder's weights stay frozen (dgrad only).  With freeze_llm = false every decoder tensor trains here as well (ps_slm_amd/full_ft.py:
+the fp32 masters of the bucket ARE the weights this forward reads; csrc/wgrad_f32.hip forms dW = dY^T X next to the dgrad that
+consumes the same dY, from the kept activations -- the normed inputs and the SwiGLU output are rebuilt, not stored), and with
+use_peft + use_emb the embedding table's gradient (lookup term + the tied head's term) joins the adapters'.  Every projector the package serves trains here -- linear-silu, linear and cov1d-linear
 (ReLU backward by the kept outputs' mask, the conv as one GEMM over the k-frame rows) and cross-attention (dq over the whole
 embedding table: tasu_f32_ca_attn_bwd, then dW_q = dq^T post) -- and so does an adapted decoder (use_peft: LoraF32 below, the
 unmerged forward y = W x + s B (A drop(x)) and the adapters' gradients into the bucket's tail).
@@ -78,8 +81,9 @@ def forward_train_fp32(model, st: StepState):
 
 
 def backward_fp32(model, st: StepState, on_ready=None):
-    """dgrad through the frozen decoder and the projector's weight gradients into ``proj.g``, all fp32.  ``on_ready(lo, hi)``: the
-    engine's gradient exchange hook, called once for the whole bucket at the end (this mode does not overlap the exchange)."""
+    """dgrad through the decoder and the weight gradients of everything that trains -- the projector, the adapters, the decoder's
+    own tensors (freeze_llm = false), the embedding table -- into ``proj.g``, all fp32.  ``on_ready(lo, hi)``: the engine's
+    gradient exchange hook, called once for the trained part of the bucket at the end (this mode does not overlap the exchange)."""
     ops, geo, llm, pr = model.ops, model.geo, model.llm, model.proj
     B, S, M = st.B, st.S, st.M
     D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
@@ -93,13 +97,27 @@ def backward_fp32(model, st: StepState, on_ready=None):
     ws = _gemm_ws(model)
     lo = lora_f32(model) if model.lora is not None else None
     drop = bool(getattr(st, "lora_drop", False))
-    xnb, actb = (buf("f32t_lora_xn", (M, D), f32), buf("f32t_lora_act", (M, I), f32)) if lo is not None else (None, None)
+    ft = model.full_ft
+    head_term = ft is not None or (model.embed_base is not None and geo.tied)   # dW of the lm_head: its own tensor, or the tied table's
+    rebuild = lo is not None or ft is not None or head_term
+    xnb, actb = (buf("f32t_lora_xn", (M, D), f32), buf("f32t_lora_act", (M, I), f32)) if rebuild else (None, None)
     dx, dn = buf("f32t_dx", (M, D), f32), buf("f32t_dn", (M, D), f32)
     dact, dgu = buf("f32t_dact", (M, I), f32), buf("f32t_dgu", (M, 2 * I), f32)
     dao, dqkv = buf("f32t_dao", (M, H * HD), f32), buf("f32t_dqkv", (M, LDQ), f32)
     lse, delta = buf("f32t_lse", (B * H * S,), f32), buf("f32t_delta", (B * H * S,), f32)
     # loss head
+    if head_term:
+        # dlogits^T xn over all rows (rows without a label hold zeros): the untied lm_head's gradient, or the head term of the tied
+        # table's, which backward_embed's lookup term is added to
+        from .full_ft import f32_wgrad
+        ops.f32_rmsnorm(xs[2 * L], llm.norm, xnb, M, D, geo.rms_eps)
+        if ft is not None:
+            ft.wgrad32(a["dlogits"][:, :V], xnb, "head", dst=model.embed_view(pr.g) if geo.tied else None)
+        else:
+            f32_wgrad(model, a["dlogits"][:, :V], xnb, model.embed_view(pr.g))
     ops.f32_gemm(a["dlogits"], wt["head"], dn, M, D, Vp, ws=ws)
+    if ft is not None:
+        ft.norm_wgrad32(dn, xs[2 * L], "norm", None)
     ops.f32_rmsnorm_bwd(dn, xs[2 * L], llm.norm, dx, M, D, geo.rms_eps, False)
     for l in range(L - 1, -1, -1):
         w, t = llm.layers[l], wt["layers"][l]
@@ -108,8 +126,15 @@ def backward_fp32(model, st: StepState, on_ready=None):
         if lo is not None and "down" in dict(lo.lp.groups):
             ops.f32_swiglu(gus[l], actb, M, I)                                       # the down projection's input, rebuilt
             lo.backward(l, "down", actb, dx, dact, M, ws, drop)
+        if ft is not None:                                                           # every weight gradient next to the dgrad of the same dY
+            ops.f32_swiglu(gus[l], actb, M, I)
+            ft.wgrad32(dx, actb, "wd", l)
         ops.f32_swiglu_bwd(dact, gus[l], dgu, M, I)
         ops.f32_gemm(dgu, t["wgu"], dn, M, D, 2 * I, ws=ws)
+        if ft is not None:
+            ops.f32_rmsnorm(xs[2 * l + 1], w["ln2"], xnb, M, D, geo.rms_eps)
+            ft.wgrad32(dgu, xnb, "wgu", l)
+            ft.norm_wgrad32(dn, xs[2 * l + 1], "ln2", l)
         if lo is not None and "gu" in dict(lo.lp.groups):
             ops.f32_rmsnorm(xs[2 * l + 1], w["ln2"], xnb, M, D, geo.rms_eps)
             lo.backward(l, "gu", xnb, dgu, dn, M, ws, drop)
@@ -118,17 +143,26 @@ def backward_fp32(model, st: StepState, on_ready=None):
         ops.f32_gemm(dx, t["wo"], dao, M, H * HD, D, ws=ws)
         if lo is not None:
             lo.backward(l, "o", aos[l], dx, dao, M, ws, drop)
+        if ft is not None:
+            ft.wgrad32(dx, aos[l], "wo", l)
         ops.f32_attn_bwd(qkvs[l], dao, a["kstart"], dqkv, lse, delta, B, S, H, G, scale)
         ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
         ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, LDQ, ws=ws)
+        if ft is not None:
+            ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
+            ft.wgrad32(dqkv, xnb, "wqkv", l)
+            ft.bias_wgrad32(dqkv, "bqkv", l)                                          # q|k|v bias: dqkv behind the inverse RoPE
+            ft.norm_wgrad32(dn, xs[2 * l], "ln1", l)
         if lo is not None and "qkv" in dict(lo.lp.groups):
             ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
             lo.backward(l, "qkv", xnb, dqkv, dn, M, ws, drop)
         ops.f32_rmsnorm_bwd(dn, xs[2 * l], w["ln1"], dx, M, D, geo.rms_eps, True)
     d["dx"] = dx
-    if model.freeze_projector:                 # (use_peft with a frozen projector: the adapters' tail of the bucket alone)
+    if model.embed_base is not None:           # the table's lookup term, on top of the head term (tied) or of zeros
+        model.backward_embed(st)
+    if model.freeze_projector:                 # (a frozen projector: the adapters' / the decoder's part of the bucket alone)
         if on_ready is not None:
-            on_ready(model.lora.base, pr.numel)
+            on_ready(model.trainable_lo, pr.numel)
         return
     # ---- merge backward + projector backward (projector.py:149-151 / :38-49 / :60-73 / :111-126 reversed); weight gradients land
     # in the flat bucket

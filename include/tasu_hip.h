@@ -562,7 +562,8 @@ int tasu_attn_decode(const void* qkv, const void* kcache, const void* vcache, co
                      void* stream);
 /* log_softmax + top-k per row of bf16 logits [M, ld]: out_val[M,k] (descending log-probs), out_idx[M,k] (token ids;
  * ties: smaller id first); the n_banned ids in `banned` (device) score -inf after the softmax
- * (MinLengthLogitsProcessor).  k in {1,2,4,6,8,16}.  workspace: M * 16 * (2 + 2k) floats (column-part partials).     */
+ * (MinLengthLogitsProcessor).  k in {1, 2, 4, 6, ..., 32} (k <= 32: 2 * n_beams for 1..16 beams).  workspace: M * 16 * (2 + 2k)
+ * floats (column-part partials).                                                                             */
 int tasu_logprob_topk(const void* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned,
                       float* out_val, int32_t* out_idx, float* workspace, int64_t workspace_floats, void* stream);
 /* One generated position of the beam search behind slam_model_asr.generate (ps-slm.py:660-675 -> HF
@@ -576,7 +577,8 @@ int tasu_logprob_topk(const void* logits, int ld, int M, int V, int k, const int
  * Also writes the next step's inputs: token ids, cache source rows (beam reorder), position ids (valid[b] +
  * t), cache slots S + t, lengths, and banned[0] = eos while the next position is below min_length else -1.
  * first = 1: vals / idx hold B rows (the prompt's last position); beams >= 1 do not exist yet.  B <= 256,
- * n_beams <= 5.                                                                                              */
+ * n_beams <= 16 (n_beams <= 5: one wave per utterance, one launch; wider: one workgroup per utterance and a one-block
+ * launch that forms the batch-wide done flag from two bits the workgroups leave in unsat[b]).                  */
 int tasu_beam_update(const float* vals, const int32_t* idx, float* run_scores, float* fin_scores, int32_t* fin_len,
                      int32_t* fin_par, int32_t* fin_tok, int32_t* is_fin, int32_t* unsat, int32_t* bp_tok,
                      int32_t* bp_par, const float* len_pow, int32_t* ctl, int32_t* done_host, const int32_t* valid,
@@ -586,13 +588,13 @@ int tasu_beam_update(const float* vals, const int32_t* idx, float* run_scores, f
 /* generate(repetition_penalty = p != 1): HF RepetitionPenaltyLogitsProcessor on the device decode loop (csrc/topk_hist.hip).
  * tasu_beam_hist_update, after tasu_beam_update: hist [B * n_beams, max_new] (row stride max_new) becomes, per row m, the history
  * of its parent row next_src[m] plus its new token next_ids[m], in place (one workgroup per utterance; parents are rows of the same
- * utterance), and hist_len[m] = ctl[0]; a no-op once ctl[1] (done) is set.  max_new <= 2048, n_beams <= 5. */
+ * utterance), and hist_len[m] = ctl[0]; a no-op once ctl[1] (done) is set.  max_new <= 2048, n_beams <= 16. */
 int tasu_beam_hist_update(int32_t* hist, int32_t* hist_len, const int32_t* ctl, const int32_t* next_src, const int32_t* next_ids,
                           int B, int n_beams, int max_new, void* stream);
 /* tasu_logprob_topk with a per-row token history hist [M, hist_ld] of hist_len[m] (<= 2048) entries and the rule
  * s' = s < 0 ? s * penalty : s / penalty, applied once per distinct history token.  mode 1 (HF greedy): on the raw logits, before the
  * softmax.  mode 0 (HF beam search): on the log-probs, not renormalised.  A history token that is also banned scores -inf; a token
- * appears at most once among the k outputs.  Same outputs, tie rule and workspace as tasu_logprob_topk; any k in 1..16;
+ * appears at most once among the k outputs.  Same outputs, tie rule and workspace as tasu_logprob_topk; any k in 1..32;
  * V <= 196608 (a column part lives in registers). */
 int tasu_logprob_topk_hist(const void* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, const int32_t* hist,
                            int hist_ld, const int32_t* hist_len, float penalty, int mode, float* out_val, int32_t* out_idx,
@@ -801,7 +803,7 @@ int tasu_f32_gather_rows(const float* dx, const int32_t* rows, float* out, int n
 int tasu_f32_attn_bwd(const float* qkv, const float* dout, const int32_t* kstart, float* dqkv, float* lse_ws, float* delta_ws, int B, int S,
                       int H, int G, float scale, void* stream);
 /* tasu_logprob_topk on fp32 logits: out_val = (x - max) - log(sum exp(x - max)) of the k best selectable columns (value descending,
- * column ascending), k <= 16; fewer than k selectable columns: (-inf, 0x7fffffff).  workspace (M * 16 * (2 + 2 k) floats, may be NULL):
+ * column ascending), k <= 32; fewer than k selectable columns: (-inf, 0x7fffffff).  workspace (M * 16 * (2 + 2 k) floats, may be NULL):
  * with it the row is split over 16 workgroups + a merge launch (a decode step's 64 rows are too few workgroups for one per row).        */
 int tasu_f32_logprob_topk(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, float* out_val,
                           int32_t* out_idx, float* workspace, int64_t workspace_floats, void* stream);

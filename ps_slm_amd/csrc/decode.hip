@@ -108,8 +108,8 @@ __global__ __launch_bounds__(64 * DEC_NW) void attn_decode_kernel(const bf16* __
 }
 
 // per row: lse over V columns, then the k best log-probs (value = logit - lse) with their column ids, descending;
-// columns listed in `banned` (n_banned ids, e.g. EOS while cur_len < min_length) score -inf.   k <= 16.
-constexpr int TOPK_MAX = 16;
+// columns listed in `banned` (n_banned ids, e.g. EOS while cur_len < min_length) score -inf.   k <= 32.
+constexpr int TOPK_MAX = 32;
 constexpr int TOPK_PARTS = 16;       // column parts per row: 64 rows x 16 parts = 1024 blocks for the 152k-column vocabulary
 // Stage 1, grid (M, TOPK_PARTS): block (row, part) scans its share of the row's columns with 16-byte loads and leaves
 //   pm/ps = max and sum exp(x - max) over its columns, pv/pi = its K largest logits (descending; ties: smaller column).
@@ -239,7 +239,22 @@ __device__ void topk_part_lists(const bf16* __restrict__ logits, int ld, int V,
     }
   }
   __syncthreads();
-  if (wave == 0) {
+  if constexpr (4 * K > 64) {                              // K > 16: the 4 K candidates are ranked by 4 K threads reading LDS
+    if (threadIdx.x < 4 * K) {
+      const float v = cv[threadIdx.x];
+      const int id = ci[threadIdx.x];
+      int rank = 0;
+      for (int d = 0; d < 4 * K; ++d) {
+        const float dv = cv[d];
+        const int di = ci[d];
+        rank += (dv > v || (dv == v && (di < id || (di == id && d < (int)threadIdx.x)))) ? 1 : 0;
+      }
+      if (rank < K) {
+        pv[slot0 * K + rank] = v;
+        pi[slot0 * K + rank] = id;
+      }
+    }
+  } else if (wave == 0) {
     static_assert(4 * K <= 64, "the four waves' candidates fit one wave");
     const bool live = lane < 4 * K;
     const float v = live ? cv[lane] : -__builtin_inff();
@@ -272,8 +287,9 @@ __global__ __launch_bounds__(256) void topk_part_kernel(const bf16* __restrict__
                                                         float* __restrict__ pv, int32_t* __restrict__ pi) {
   __shared__ float red[4];
   __shared__ float wtau[4];
-  __shared__ float cand_v[CAND_CAP];
-  __shared__ int cand_i[CAND_CAP];
+  constexpr int CAP = K <= 16 ? CAND_CAP : 2 * CAND_CAP; // (up to 4 K - 3 per-thread maxima alone can reach tau)
+  __shared__ float cand_v[CAP];
+  __shared__ int cand_i[CAP];
   __shared__ int cand_n;
   const int row = blockIdx.x, part = blockIdx.y;
   [[maybe_unused]] const int g = part;                   // (TASU_ATTN_STAMP's workgroup test: row == 0 && g == 0)
@@ -346,7 +362,7 @@ __global__ __launch_bounds__(256) void topk_part_kernel(const bf16* __restrict__
           s += __expf(f - m);
           if (f >= tau && f > -__builtin_inff() && !is_banned(c)) {
             const int slot = atomicAdd(&cand_n, 1);
-            if (slot < CAND_CAP) {
+            if (slot < CAP) {
               cand_v[slot] = f;
               cand_i[slot] = c;
             }
@@ -358,7 +374,7 @@ __global__ __launch_bounds__(256) void topk_part_kernel(const bf16* __restrict__
   TASU_ATTN_STAMP(12);
   s = block_sum<4>(s, red);                              // (its barriers also publish the candidates)
   const int n_cand = cand_n;
-  if (n_cand > CAND_CAP) {                                 // block-uniform
+  if (n_cand > CAP) {                                      // block-uniform
     topk_part_lists<K>(logits, ld, V, banned, n_banned, pm, ps, pv, pi);
     return;
   }
@@ -368,7 +384,23 @@ __global__ __launch_bounds__(256) void topk_part_kernel(const bf16* __restrict__
     ps[slot0] = s;
   }
   TASU_ATTN_STAMP(13);
-  if (wave == 0) {
+  if constexpr (CAP > 64) {                                // K > 16: up to 128 candidates, ranked by as many threads reading LDS
+    const int t = threadIdx.x;
+    if (t < n_cand) {
+      const float v = cand_v[t];
+      const int id = cand_i[t];
+      int rank = 0;
+      for (int d = 0; d < n_cand; ++d) rank += (cand_v[d] > v || (cand_v[d] == v && cand_i[d] < id)) ? 1 : 0;
+      if (rank < K) {
+        pv[slot0 * K + rank] = v;
+        pi[slot0 * K + rank] = id;
+      }
+    }
+    if (t >= n_cand && t < K) {                            // fewer than K selectable columns in this part
+      pv[slot0 * K + t] = -__builtin_inff();
+      pi[slot0 * K + t] = 0x7fffffff;
+    }
+  } else if (wave == 0) {
     const bool live = lane < n_cand;
     const float v = live ? cand_v[lane] : -__builtin_inff();
     const int id = live ? cand_i[lane] : 0x7fffffff;
@@ -455,7 +487,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const float* __restrict_
 // reorder, position ids, cache slots, lengths, the EOS ban while cur < min_length), so the whole decode step replays as one
 // hipGraph with no host round trip; ctl[0] = positions generated so far, ctl[1] = done (then the kernel is a no-op).
 constexpr float BEAM_NEG = -1.0e9f;
-constexpr int BEAM_MAX_NB = 5;          // nb * 2 nb candidates must fit the 64-bit `used` mask below
+constexpr int BEAM_MAX_NB = 5;          // one wave per utterance: nb * 2 nb candidates fit its 64 lanes (wider: beam_update_wide_kernel)
 struct BeamArgs {
   const float* vals;          // [B * nb, K] (first call: [B, K], beams >= 1 absent)
   const int32_t* idx;
@@ -481,6 +513,8 @@ struct BeamArgs {
   int B, nb, max_new, eos, min_length, S, first;
 };
 
+// (More than BEAM_MAX_NB beams: beam_update_wide_kernel below, whose wave 0 repeats this kernel's statements from "lanes i < K" on --
+// a fix here belongs there too.)
 // One WAVE per utterance (16 utterances per pass of a 1024-thread block): lane c < nb * K holds candidate (beam c / K, k-th best
 // of that beam); every selection is a rank computed with wave shuffles -- rank = number of candidates that precede this one in
 // the (score desc, beam asc, token asc, index asc) order -- so there are no per-thread arrays and no serial scans (the first,
@@ -611,6 +645,171 @@ __global__ __launch_bounds__(1024) void beam_update_kernel(BeamArgs p) {
       if (still) atomicOr(&s_unsat_any, 1);
       if (!all_stop) atomicAnd(&s_stop_all, 0);
     }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int done = !(s_unsat_any && !s_stop_all);
+    p.ctl[0] = cur + 1;
+    p.ctl[1] = done;
+    p.banned[0] = (cur + 1 < p.min_length) ? p.eos : -1;
+    if (p.done_host) __hip_atomic_store(p.done_host, done ? cur + 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// More than BEAM_MAX_NB beams (nb <= BEAM_WIDE_MAX_NB, up to 16 * 32 = 512 candidates): one WORKGROUP per utterance.  Thread c < nb * K
+// holds candidate c; the candidates meet in LDS and every thread counts the candidates that precede its own in the (score desc,
+// beam asc, token asc, index asc) order by reading them back (all threads read the same address: an LDS broadcast).  The K best then
+// fit one wave (K <= 32, nb + K <= 48), and wave 0 runs beam_update_kernel's selection of the running set, the finished-hypothesis
+// merge and the unsat test on them, statement for statement (a fix to one of the two kernels belongs in the other; the tests hold
+// both to BeamState after every step).  The batch-wide `done` needs every utterance's verdict: a workgroup leaves two bits in its
+// own unsat[b] -- bit 0 = the utterance can still improve, bit 1 = one of its K best does not stop -- and beam_finish_kernel (one
+// block, the next launch on the stream) reduces them, puts unsat[b] back to 0 / 1 and writes ctl / banned / done_host: no workgroup
+// waits for another, the value cannot depend on the order in which they finish, and the state is the call's own (two decodes on two
+// streams do not meet).
+constexpr int BEAM_WIDE_MAX_NB = 16;
+constexpr int BEAM_WIDE_THREADS = 2 * BEAM_WIDE_MAX_NB * BEAM_WIDE_MAX_NB;
+__global__ __launch_bounds__(BEAM_WIDE_THREADS) void beam_update_wide_kernel(BeamArgs p) {
+  __shared__ float s_cs[BEAM_WIDE_THREADS];
+  __shared__ int s_ct[BEAM_WIDE_THREADS];
+  __shared__ float s_top_lp[2 * BEAM_WIDE_MAX_NB];
+  __shared__ int s_top_tok[2 * BEAM_WIDE_MAX_NB], s_top_beam[2 * BEAM_WIDE_MAX_NB];
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int nb = p.nb, K = 2 * nb, NC = nb * K;
+  const int cur = p.ctl[0];
+  if (p.ctl[1]) return;                                   // finished earlier: leave every output as it is (block-uniform)
+  const float lp_now = p.len_pow[cur + 1];
+  // ---- candidates
+  const int j = t / K, k = t - j * K;
+  float cs = -__builtin_inff();
+  int ct = 0;
+  if (t < NC) {
+    float v = BEAM_NEG;
+    if (!p.first || j == 0) {
+      const size_t row = p.first ? (size_t)b : (size_t)b * nb + j;
+      v = p.vals[row * K + k];
+      ct = p.idx[row * K + k];
+    }
+    cs = v + p.run_scores[b * nb + j];
+  }
+  s_cs[t] = cs;
+  s_ct[t] = ct;
+  __syncthreads();
+  // ---- top K by (score desc, beam asc, token asc, candidate index asc)
+  if (t < NC) {
+    int rank = 0;
+    for (int d0 = 0; d0 < NC; d0 += K) {                  // beam jd = d0 / K
+      const int jd = d0 / K;
+      for (int d = d0; d < d0 + K; ++d) {
+        const float sd = s_cs[d];
+        const int td = s_ct[d];
+        const bool before = sd > cs || (sd == cs && (jd < j || (jd == j && (td < ct || (td == ct && d < t)))));
+        rank += before ? 1 : 0;
+      }
+    }
+    if (rank < K) {
+      s_top_lp[rank] = cs;
+      s_top_tok[rank] = ct;
+      s_top_beam[rank] = j;
+    }
+  }
+  __syncthreads();
+  if (t >= 64) return;
+  // ---- wave 0, lanes i < K: the K best in order (from here on: beam_update_kernel's statements on one wave)
+  const int lane = t;
+  const bool is_top = lane < K;
+  const float top_lp = is_top ? s_top_lp[lane] : 0.f;
+  const int tok = is_top ? s_top_tok[lane] : 0, beam = is_top ? s_top_beam[lane] : 0;
+  const bool stop = is_top && (tok == p.eos || cur + 1 >= p.max_new);
+  const float run_lp = is_top ? top_lp + (stop ? BEAM_NEG : 0.f) : -__builtin_inff();
+  const bool all_stop = __all(!is_top || stop);
+  // running beams of the next step: stable top nb of run_lp
+  int r_run = 0;
+  for (int d = 0; d < K; ++d) {
+    const float sd = __shfl(run_lp, d, 64);
+    r_run += (sd > run_lp || (sd == run_lp && d < lane)) ? 1 : 0;
+  }
+  const bool runs = is_top && r_run < nb;
+  if (runs) {
+    const size_t o = ((size_t)cur * p.B + b) * nb + r_run;
+    p.bp_tok[o] = tok;
+    p.bp_par[o] = beam;
+    const int m = b * nb + r_run;
+    p.next_ids[m] = tok;
+    p.next_src[m] = b * nb + beam;
+    p.next_pos[m] = p.valid[b] + cur;
+    p.next_slot[m] = p.S + cur;
+    p.next_lens[m] = p.S + cur + 1;
+  }
+  const float best_run_lp = __shfl(run_lp, __ffsll((long long)__ballot(runs && r_run == 0)) - 1, 64);   // new running score of slot 0
+  // ---- finished hypotheses: stable top nb of [kept (lanes 0..nb-1) | new (lanes nb..nb+K-1)]
+  const bool unsat = p.unsat[b] != 0;
+  const bool is_old = lane < nb, is_new = lane >= nb && lane < nb + K;
+  const int src = lane - nb;                             // index into the K best for the new entries
+  float m_sc = -__builtin_inff();
+  int m_len = 0, m_par = 0, m_tok = 0, m_fin = 0;
+  {
+    const float t_lp = __shfl(top_lp, src < 0 ? 0 : src, 64);
+    const int t_tok = __shfl(tok, src < 0 ? 0 : src, 64), t_beam = __shfl(beam, src < 0 ? 0 : src, 64);
+    const int t_stop = __shfl((int)stop, src < 0 ? 0 : src, 64);
+    if (is_old) {
+      m_sc = p.fin_scores[b * nb + lane];
+      m_len = p.fin_len[b * nb + lane];
+      m_par = p.fin_par[b * nb + lane];
+      m_tok = p.fin_tok[b * nb + lane];
+      m_fin = p.is_fin[b * nb + lane];
+    } else if (is_new) {
+      const bool just = t_stop && src < nb;
+      float sc = t_lp / lp_now;
+      sc = sc + (unsat ? 0.f : BEAM_NEG);
+      sc = sc + (just ? 0.f : BEAM_NEG);
+      m_sc = sc;
+      m_len = cur + 1;
+      m_par = t_beam;
+      m_tok = t_tok;
+      m_fin = just ? 1 : 0;
+    }
+  }
+  int r_fin = 0;
+  for (int d = 0; d < nb + K; ++d) {
+    const float sd = __shfl(m_sc, d, 64);
+    r_fin += (sd > m_sc || (sd == m_sc && d < lane)) ? 1 : 0;
+  }
+  const bool kept = (is_old || is_new) && r_fin < nb;
+  // every lane has read its old entry: the wave is converged here, so the writes below cannot overtake those reads
+  if (kept) {
+    p.fin_scores[b * nb + r_fin] = m_sc;
+    p.fin_len[b * nb + r_fin] = m_len;
+    p.fin_par[b * nb + r_fin] = m_par;
+    p.fin_tok[b * nb + r_fin] = m_tok;
+    p.is_fin[b * nb + r_fin] = m_fin;
+  }
+  if (runs) p.run_scores[b * nb + r_run] = run_lp;
+  // ---- can a running beam still beat the worst kept hypothesis?
+  float min_fin = kept ? m_sc : __builtin_inff();
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) min_fin = fminf(min_fin, __shfl_xor(min_fin, o, 64));
+  const float best_run = best_run_lp / lp_now;           // the new cur is cur + 1: the same power
+  const bool improve = __any(kept && best_run > (m_fin ? min_fin : BEAM_NEG));
+  const bool still = unsat && improve;
+  if (lane == 0) {
+    p.unsat[b] = (still ? 1 : 0) | (all_stop ? 0 : 2);     // (bit 1: for beam_finish_kernel, which takes it out again)
+  }
+}
+// The end of a wide beam update: done = no utterance can still improve or every candidate of every utterance stopped.
+__global__ __launch_bounds__(256) void beam_finish_kernel(BeamArgs p) {
+  __shared__ int s_unsat_any, s_stop_all;
+  const int cur = p.ctl[0];
+  if (p.ctl[1]) return;
+  if (threadIdx.x == 0) {
+    s_unsat_any = 0;
+    s_stop_all = 1;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < p.B) {
+    const int f = p.unsat[threadIdx.x];
+    p.unsat[threadIdx.x] = f & 1;
+    if (f & 1) atomicOr(&s_unsat_any, 1);
+    if (f & 2) atomicAnd(&s_stop_all, 0);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -783,6 +982,9 @@ extern "C" int tasu_logprob_topk(const void* logits, int ld, int M, int V, int k
     return TASU_OK;
   switch (k) {
     TOPK_CASE(1) TOPK_CASE(2) TOPK_CASE(4) TOPK_CASE(6) TOPK_CASE(8) TOPK_CASE(16)
+    // the widths of 5, 6, 7 and 9..16 beams (k = 2 * num_beams)
+    TOPK_CASE(10) TOPK_CASE(12) TOPK_CASE(14) TOPK_CASE(18) TOPK_CASE(20) TOPK_CASE(22) TOPK_CASE(24) TOPK_CASE(26) TOPK_CASE(28)
+    TOPK_CASE(30) TOPK_CASE(32)
     default:
       return TASU_ERR_ARG;
   }
@@ -803,10 +1005,15 @@ extern "C" int tasu_beam_update(const float* vals, const int32_t* idx, float* ru
   if (!vals || !idx || !run_scores || !fin_scores || !fin_len || !fin_par || !fin_tok || !is_fin || !unsat || !bp_tok || !bp_par ||
       !len_pow || !ctl || !valid || !next_ids || !next_src || !next_pos || !next_slot || !next_lens || !banned)
     return TASU_ERR_ARG;
-  if (B <= 0 || B > 256 || n_beams <= 0 || n_beams > BEAM_MAX_NB || max_new <= 0 || S <= 0) return TASU_ERR_ARG;
+  if (B <= 0 || B > 256 || n_beams <= 0 || n_beams > BEAM_WIDE_MAX_NB || max_new <= 0 || S <= 0) return TASU_ERR_ARG;
   BeamArgs a{vals, idx, run_scores, fin_scores, fin_len, fin_par, fin_tok, is_fin, unsat, bp_tok, bp_par, len_pow, ctl,
              done_host, valid, next_ids, next_src, next_pos, next_slot, next_lens, banned, B, n_beams, max_new, eos,
              min_length, S, first};
+  if (n_beams > BEAM_MAX_NB) {                            // a workgroup per utterance, then the batch-wide done flag
+    TASU_LAUNCH(beam_update_wide_kernel, dim3(B), dim3(BEAM_WIDE_THREADS), 0, (hipStream_t)stream, a);
+    TASU_LAUNCH(beam_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return TASU_OK;
+  }
   TASU_LAUNCH(beam_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
   return TASU_OK;
 }

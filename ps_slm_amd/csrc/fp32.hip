@@ -958,15 +958,16 @@ __global__ __launch_bounds__(256) void f32_topk_part_kernel(const float* __restr
     if (bid == 0x7fffffff) pvv = -__builtin_inff(), pii = 0x7fffffff;
   }
 }
-__global__ __launch_bounds__(256) void f32_topk_merge_kernel(const float* __restrict__ pm, const float* __restrict__ ps,
+template <int NT>                                          // NT >= 16 k threads: one candidate per thread
+__global__ __launch_bounds__(NT) void f32_topk_merge_kernel(const float* __restrict__ pm, const float* __restrict__ ps,
                                                              const float* __restrict__ pv, const int32_t* __restrict__ pi, int k,
                                                              float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
-  __shared__ float cv[F32_TOPK_PARTS * 16];
-  __shared__ int ci[F32_TOPK_PARTS * 16];
+  __shared__ float cv[NT];
+  __shared__ int ci[NT];
   __shared__ float stat[2];
   __shared__ int nvalid;
   const int row = blockIdx.x, t = threadIdx.x, lane = t & 63;
-  const int n = F32_TOPK_PARTS * k;                      // <= 256: one candidate per thread
+  const int n = F32_TOPK_PARTS * k;                      // <= NT: one candidate per thread
   if (t == 0) nvalid = 0;
   float v = -__builtin_inff();
   int id = 0x7fffffff;
@@ -1421,9 +1422,11 @@ extern "C" int tasu_f32_ce(const float* logits, int ld, const int32_t* shift_lab
   return TASU_OK;
 }
 
+int tasu_f32_topk_part_wide(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, float* pm, float* ps,
+                            float* pv, int32_t* pi, hipStream_t stream);      // csrc/fp32_topk_wide.hip
 extern "C" int tasu_f32_logprob_topk(const float* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, float* out_val,
                                      int32_t* out_idx, float* workspace, int64_t workspace_floats, void* stream) {
-  if (!logits || !out_val || !out_idx || M <= 0 || V <= 0 || ld < V || k <= 0 || k > 16 || n_banned < 0 || (n_banned > 0 && !banned))
+  if (!logits || !out_val || !out_idx || M <= 0 || V <= 0 || ld < V || k <= 0 || k > 32 || n_banned < 0 || (n_banned > 0 && !banned))
     return TASU_ERR_ARG;
   // with a workspace of M * 16 * (2 + 2 k) floats, 16-byte aligned rows and a vocabulary the parts hold in registers: two launches,
   // the row split over 16 workgroups; otherwise one workgroup per row
@@ -1435,9 +1438,15 @@ extern "C" int tasu_f32_logprob_topk(const float* logits, int ld, int M, int V, 
     float* ps = pm + slots;
     float* pv = ps + slots;
     int32_t* pi = (int32_t*)(pv + slots * k);
-    TASU_LAUNCH(f32_topk_part_kernel, dim3(M, F32_TOPK_PARTS), dim3(256), 0, (hipStream_t)stream, logits, ld, V, k, banned, n_banned, pm, ps, pv,
-                pi);
-    TASU_LAUNCH(f32_topk_merge_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, pm, ps, pv, pi, k, out_val, out_idx);
+    if (k <= 16) {
+      TASU_LAUNCH(f32_topk_part_kernel, dim3(M, F32_TOPK_PARTS), dim3(256), 0, (hipStream_t)stream, logits, ld, V, k, banned,
+                  n_banned, pm, ps, pv, pi);
+      TASU_LAUNCH(f32_topk_merge_kernel<256>, dim3(M), dim3(256), 0, (hipStream_t)stream, pm, ps, pv, pi, k, out_val, out_idx);
+    } else {
+      // (csrc/fp32_topk_wide.hip: a kernel added to this file changes the code the compiler generates for its neighbours)
+      if (int rc = tasu_f32_topk_part_wide(logits, ld, M, V, k, banned, n_banned, pm, ps, pv, pi, (hipStream_t)stream)) return rc;
+      TASU_LAUNCH(f32_topk_merge_kernel<512>, dim3(M), dim3(512), 0, (hipStream_t)stream, pm, ps, pv, pi, k, out_val, out_idx);
+    }
     return TASU_OK;
   }
   TASU_LAUNCH(f32_logprob_topk_kernel, dim3(M), dim3(1024), 0, (hipStream_t)stream, logits, ld, V, k, banned, n_banned, out_val, out_idx);

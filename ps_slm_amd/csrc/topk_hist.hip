@@ -17,7 +17,7 @@
 
 namespace {
 constexpr int HT_PARTS = 16;          // column parts per row (the workspace layout of tasu_logprob_topk)
-constexpr int HT_PCAND = 64;          // threshold form: candidates a part ranks in one wave
+constexpr int HT_PCAND = 64;          // threshold form: candidates a part ranks in one wave (k <= 16; k <= 32: twice as many, ranked through LDS)
 constexpr int HT_HIST_MAX = 2048;     // history entries per row (the decode context limit)
 constexpr int HT_NONE = 0x7fffffff;
 
@@ -37,7 +37,7 @@ struct HtVec<float, 4> {
 // Stage 1, grid (M, 16), 256 threads: the part's columns live in registers (one read).  pm / ps = max and sum exp(x - max) over
 // its columns (mode 1: history columns penalised first), pv / pi = its k best selectable columns (value descending, column
 // ascending; mode 0: history columns are not selectable here) by the threshold form, or on massive ties by k rounds of block argmax.
-template <typename T, int VEC, int MAXC, bool FAST>
+template <typename T, int VEC, int MAXC, bool FAST, int PCAND>
 __global__ __launch_bounds__(256) void topk_part_hist_kernel(const T* __restrict__ logits, int ld, int V, int k,
                                                              const int32_t* __restrict__ banned, int n_banned,
                                                              const int32_t* __restrict__ hist, int hist_ld,
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(256) void topk_part_hist_kernel(const T* __restrict
   __shared__ float wtau[4];
   __shared__ float bv[4];
   __shared__ int bi[4];
-  __shared__ float cand_v[HT_PCAND];
-  __shared__ int cand_i[HT_PCAND];
+  __shared__ float cand_v[PCAND];
+  __shared__ int cand_i[PCAND];
   __shared__ int cand_n;
   __shared__ unsigned hbits[NWORD];
   const int row = blockIdx.x, part = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void topk_part_hist_kernel(const T* __restrict
         s += FAST ? __expf(v - m) : expf(v - m);
         if (v >= tau && ((selm[i] >> j) & 1u)) {
           const int slot = atomicAdd(&cand_n, 1);
-          if (slot < HT_PCAND) cand_v[slot] = v, cand_i[slot] = (v0 + t + i * 256) * VEC + j;
+          if (slot < PCAND) cand_v[slot] = v, cand_i[slot] = (v0 + t + i * 256) * VEC + j;
         }
       }
     }
@@ -136,8 +136,17 @@ __global__ __launch_bounds__(256) void topk_part_hist_kernel(const T* __restrict
   const size_t slot0 = (size_t)row * HT_PARTS + part;
   if (t == 0) pm[slot0] = m, ps[slot0] = s;
   const int n_cand = cand_n;
-  if (n_cand <= HT_PCAND) {
-    if (wave == 0) {
+  if (n_cand <= PCAND) {
+    if constexpr (PCAND > 64) {                            // as many threads as candidates rank them by reading LDS
+      if (t < n_cand) {
+        const float v = cand_v[t];
+        const int id = cand_i[t];
+        int rank = 0;
+        for (int d = 0; d < n_cand; ++d) rank += (cand_v[d] > v || (cand_v[d] == v && cand_i[d] < id)) ? 1 : 0;
+        if (rank < k) pv[slot0 * k + rank] = v, pi[slot0 * k + rank] = id;
+      }
+      if (t >= n_cand && t < k) pv[slot0 * k + t] = -__builtin_inff(), pi[slot0 * k + t] = HT_NONE;
+    } else if (wave == 0) {
       const bool live = lane < n_cand;
       const float v = live ? cand_v[lane] : -__builtin_inff();
       const int id = live ? cand_i[lane] : HT_NONE;
@@ -287,12 +296,42 @@ __global__ __launch_bounds__(256) void beam_hist_update_kernel(int32_t* __restri
   }
 }
 
+// More than 5 beams: n_beams * max_new ints no longer fit the LDS a launch gets by default, so the rows are staged HT_WIDE_COLS
+// positions at a time (dst[r, i] = src[parent r, i] for the SAME i: a pass only reads and writes its own columns).
+constexpr int HT_WIDE_NB = 16, HT_WIDE_COLS = 512;
+__global__ __launch_bounds__(256) void beam_hist_update_wide_kernel(int32_t* __restrict__ hist, int32_t* __restrict__ hist_len,
+                                                                    const int32_t* __restrict__ ctl, const int32_t* __restrict__ next_src,
+                                                                    const int32_t* __restrict__ next_ids, int nb, int M, int max_new) {
+  __shared__ int stage[HT_WIDE_NB * HT_WIDE_COLS];
+  const int n = ctl[0];
+  if (ctl[1] || n < 1 || n > max_new) return;             // (block-uniform)
+  const int m0 = blockIdx.x * nb, rows = min(nb, M - m0);
+  for (int c0 = 0; c0 < n - 1; c0 += HT_WIDE_COLS) {
+    const int w = min(HT_WIDE_COLS, n - 1 - c0);
+    for (int r = 0; r < rows; ++r) {
+      int src = next_src[m0 + r];
+      if (src < m0 || src >= m0 + rows) src = m0 + r;
+      for (int i = threadIdx.x; i < w; i += 256) stage[r * HT_WIDE_COLS + i] = hist[(size_t)src * max_new + c0 + i];
+    }
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      int32_t* dst = hist + (size_t)(m0 + r) * max_new + c0;
+      for (int i = threadIdx.x; i < w; i += 256) dst[i] = stage[r * HT_WIDE_COLS + i];
+    }
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < rows) {
+    hist[(size_t)(m0 + threadIdx.x) * max_new + n - 1] = next_ids[m0 + threadIdx.x];
+    hist_len[m0 + threadIdx.x] = n;
+  }
+}
+
 template <typename T, int VEC, int MAXC, bool FAST>
 int topk_hist_launch(const T* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, const int32_t* hist, int hist_ld,
                      const int32_t* hist_len, float penalty, int mode, float* out_val, int32_t* out_idx, float* workspace,
                      int64_t workspace_floats, hipStream_t stream) {
   if (!logits || !out_val || !out_idx || !workspace || !hist || !hist_len || M <= 0 || V <= 0 || ld < V || ld % VEC ||
-      ((uintptr_t)logits & 15) || k <= 0 || k > 16 || n_banned < 0 || (n_banned > 0 && !banned) || hist_ld <= 0 ||
+      ((uintptr_t)logits & 15) || k <= 0 || k > 32 || n_banned < 0 || (n_banned > 0 && !banned) || hist_ld <= 0 ||
       !(penalty > 0.f) || (mode != 0 && mode != 1))
     return TASU_ERR_ARG;
   const int nv = (V + VEC - 1) / VEC, per = (nv + HT_PARTS - 1) / HT_PARTS;
@@ -304,8 +343,13 @@ int topk_hist_launch(const T* logits, int ld, int M, int V, int k, const int32_t
   float* pv = ps + slots;
   int32_t* pi = (int32_t*)(pv + slots * k);
   const int cap = HT_PARTS * k + (mode == 0 ? (hist_ld < HT_HIST_MAX ? hist_ld : HT_HIST_MAX) : 0);
-  TASU_LAUNCH((topk_part_hist_kernel<T, VEC, MAXC, FAST>), dim3(M, HT_PARTS), dim3(256), 0, stream, logits, ld, V, k, banned, n_banned, hist,
-              hist_ld, hist_len, penalty, mode, pm, ps, pv, pi);
+  if (k <= 16) {
+    TASU_LAUNCH((topk_part_hist_kernel<T, VEC, MAXC, FAST, HT_PCAND>), dim3(M, HT_PARTS), dim3(256), 0, stream, logits, ld, V, k, banned,
+                n_banned, hist, hist_ld, hist_len, penalty, mode, pm, ps, pv, pi);
+  } else {
+    TASU_LAUNCH((topk_part_hist_kernel<T, VEC, MAXC, FAST, 2 * HT_PCAND>), dim3(M, HT_PARTS), dim3(256), 0, stream, logits, ld, V, k, banned,
+                n_banned, hist, hist_ld, hist_len, penalty, mode, pm, ps, pv, pi);
+  }
   TASU_LAUNCH((topk_merge_hist_kernel<T, FAST>), dim3(M), dim3(64), (size_t)cap * 8, stream, logits, ld, V, k, banned, n_banned, hist, hist_ld,
               hist_len, penalty, mode, cap, pm, ps, pv, pi, out_val, out_idx);
   return TASU_OK;
@@ -328,9 +372,14 @@ extern "C" int tasu_f32_logprob_topk_hist(const float* logits, int ld, int M, in
 
 extern "C" int tasu_beam_hist_update(int32_t* hist, int32_t* hist_len, const int32_t* ctl, const int32_t* next_src,
                                      const int32_t* next_ids, int B, int n_beams, int max_new, void* stream) {
-  if (!hist || !hist_len || !ctl || !next_src || !next_ids || B <= 0 || n_beams <= 0 || n_beams > 5 || max_new <= 0 ||
+  if (!hist || !hist_len || !ctl || !next_src || !next_ids || B <= 0 || n_beams <= 0 || n_beams > HT_WIDE_NB || max_new <= 0 ||
       max_new > HT_HIST_MAX)
     return TASU_ERR_ARG;
+  if (n_beams > 5) {
+    TASU_LAUNCH(beam_hist_update_wide_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, hist, hist_len, ctl, next_src, next_ids, n_beams,
+                B * n_beams, max_new);
+    return TASU_OK;
+  }
   TASU_LAUNCH(beam_hist_update_kernel, dim3(B), dim3(256), (size_t)n_beams * max_new * sizeof(int), (hipStream_t)stream, hist, hist_len, ctl,
               next_src, next_ids, n_beams, B * n_beams, max_new);
   return TASU_OK;

@@ -1,6 +1,6 @@
 """Decode loop of ``slam_model_asr.generate`` (Multitask/model/ps-slm.py:539-677) on the gfx950 kernels: prefill with
 the training forward kernels, then one single-token step per generated position with a per-beam KV cache.  The beam
-bookkeeping of HF ``generate(num_beams=4, do_sample=False, early_stopping=False)`` (transformers generation/utils.py
+bookkeeping of HF ``generate(num_beams=1..16, do_sample=False, early_stopping=False)`` (transformers generation/utils.py
 ``_beam_search``; dependency not in the reference tree) runs ON THE DEVICE (``tasu_beam_update``: selection among the
 rows' 2*nb best log-probs, finished-hypothesis heap, early-stop heuristic, and the next step's token ids / cache rows /
 positions), so a generated position is ONE hipGraph replay with no host round trip; the host only polls a pinned
@@ -20,7 +20,7 @@ import torch
 from .model import HD, StepState, rup
 
 NEG = -1.0e9
-BEAM_MAX_NB, BEAM_MAX_B, DECODE_MAX_CTX = 5, 256, 2048   # limits of tasu_beam_update / tasu_decode_step_prologue / tasu_attn_decode
+BEAM_MAX_NB, BEAM_MAX_B, DECODE_MAX_CTX = 16, 256, 2048   # limits of tasu_beam_update (beams, utterances) / tasu_attn_decode
 log = logging.getLogger(__name__)
 _warned_prompt_not_penalised = False
 
@@ -179,11 +179,31 @@ def effective_min_length(min_length, S):
     return max(int(min_length) - int(S), 0)
 
 
+def check_kv_cache_fits(model, B, nb, ctx, elem_bytes, names):
+    """The K and V caches ``names`` of a decode with B * nb rows: L * rows * ctx * G * 128 * 2 * elem_bytes bytes, which grows with
+    the beam width.  What the model's buffers do not hold yet must fit the device's free memory (the allocator's cached blocks
+    included): a ValueError with the sizes here, not an allocator error in the middle of decode.  A cache that has to grow counts
+    with its full new size: the model's grow-only buffers (``_buf``) allocate the larger tensor while the smaller one is still held,
+    so both exist for a moment.  Host-side queries only, no launch."""
+    geo = model.geo
+    each = geo.llm_layers * B * nb * ctx * geo.llm_kv_heads * HD * elem_bytes
+    if model.device.type != "cuda":
+        return 2 * each
+    held = [model._ws.get(n) for n in names]
+    grow = sum(each for t in held if t is None or t.numel() * t.element_size() < each or t.element_size() != elem_bytes)
+    free = torch.cuda.mem_get_info(model.device)[0] + torch.cuda.memory_reserved(model.device) - torch.cuda.memory_allocated(model.device)
+    if grow > free:
+        raise ValueError(f"num_beams={nb} x {B} utterances at context {ctx}: the KV cache takes {2 * each} bytes ({geo.llm_layers} layers x "
+                         f"{B * nb} rows x {ctx} positions x {geo.llm_kv_heads * HD} x 2 x {elem_bytes}), {grow} of them still to allocate, "
+                         f"and the device has {free} bytes free")
+    return 2 * each
+
+
 def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention,
-                  repetition_penalty=1.0):
-    """Checks a generate() call against the limits of the device beam search (tasu_beam_update, tasu_decode_step_prologue:
-    include/tasu_hip.h) and the context limit ``max_ctx`` of the caller's cache attention, BEFORE any prefill.  Returns
-    (min_length in generated positions, eos, pad)."""
+                  repetition_penalty=1.0, kv_elem_bytes=2, kv_names=("dec_kc", "dec_vc")):
+    """Checks a generate() call against the limits of the device beam search (tasu_beam_update: include/tasu_hip.h), the context
+    limit ``max_ctx`` of the caller's cache attention and the device's free memory (the KV caches ``kv_names``), BEFORE any
+    prefill.  Returns (min_length in generated positions, eos, pad)."""
     B, S = st.B, st.S
     if not 1 <= nb <= BEAM_MAX_NB:
         raise ValueError(f"num_beams={nb}: the device beam search serves 1..{BEAM_MAX_NB} beams")
@@ -202,6 +222,7 @@ def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_toke
             _warned_prompt_not_penalised = True
             log.warning("Passing `repetition_penalty` with `inputs_embeds` and without `input_ids` to `generate` will apply the penalty "
                         "only to newly generated tokens, not to the prompt.")
+    check_kv_cache_fits(model, B, nb, S + max_new_tokens, kv_elem_bytes, kv_names)
     eos = model.geo.eos_id if eos_token_id is None else eos_token_id
     pad = eos if pad_token_id is None else pad_token_id
     return effective_min_length(min_length, S), eos, pad

@@ -246,7 +246,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, F32_MAX_CTX,
-                                         "the fp32 attention's", repetition_penalty)
+                                         "the fp32 attention's", repetition_penalty, kv_elem_bytes=4, kv_names=("f32_kc", "f32_vc"))
     B, S, nb = st.B, st.S, num_beams
     ctx = S + max_new_tokens
     M, K = B * nb, 2 * nb

@@ -53,7 +53,7 @@ class HipOps:
         # Allocated up front (never inside a hipGraph capture); all GEMMs of one HipOps run on one stream.
         self.gemm_ws = torch.zeros(GEMM_WS_BYTES, dtype=torch.uint8, device="cuda")
         self._gemm_ws_alt = {}         # further ones for launch sequences that may run on another stream (alt_workspace)
-        self.topk_ws = torch.empty(1024 * 16 * 34, dtype=torch.float32, device="cuda")   # tasu_logprob_topk partials, M <= 1024
+        self.topk_ws = torch.empty(1024 * 16 * 66, dtype=torch.float32, device="cuda")   # tasu_logprob_topk partials, M <= 1024 at k = 32
         # decode-step GEMMs: the single-launch weight-streaming kernels (csrc/gemm_stream.hip) where they serve the shape,
         # the split-K + finish kernels (csrc/gemm_skinny.hip) otherwise.
         self.use_stream = True          # (tests / tools flip the attribute for A/B runs)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 22
+#define TASU_ABI_VERSION 23
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -127,6 +127,13 @@ int tasu_gemm_nt_bf16_streamk(const void* A, int lda, const void* B, int ldb, vo
 #define TASU_GEMM_PLAN_TILES 9                /* 128-row tiles of gemm.hip (at most 64 rows, or a forced kernel) */
 /* (-1: the arguments would be rejected) */
 int tasu_gemm_plan(int M, int N, int K, int out_mode, int with_workspace);
+/* Likewise for tasu_gemm_gate_up_swiglu_ws (with_workspace != 0) / tasu_gemm_gate_up_swiglu: what the call launches.  Returns one of: */
+#define TASU_GEMM_GU_PLAN_PIPE 1              /* loader-wave kernel, 256 x 128 tiles (64 act columns) */
+#define TASU_GEMM_GU_PLAN_PP 2                /* 256 x 256 eight-wave kernel (128 act columns), whole tiles */
+#define TASU_GEMM_GU_PLAN_PP_PLUS_PIPE 3      /* whole rounds of 256 x 256 tiles + the remaining columns on 256 x 128 tiles: two launches */
+#define TASU_GEMM_GU_PLAN_PP_STREAMK 4        /* 256 x 256 tiles cut along K, one range per workgroup */
+/* (-1: the arguments would be rejected) */
+int tasu_gemm_gate_up_plan(int M, int I, int K, int with_workspace);
 /* Host-side restatement of that schedule through the kernel's own code (no GPU needed; tests): the work-item lists of `grid`
  * workgroups for `tiles` output tiles of `pairs` K-tile pairs (K = 128 * pairs).  items[w][i] = {tile, first K-tile, K-tiles,
  * role: 0 whole tile, 1 partial-tile producer, 2 tile owner}, max_items per workgroup; counts[w] = items of workgroup w.

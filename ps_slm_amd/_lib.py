@@ -124,6 +124,7 @@ PROTOTYPES.update({
     "tasu_gemm_qkv_rope": [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
     "tasu_gemm_dswiglu": [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, i64, vp],
     "tasu_gemm_plan": [i32, i32, i32, i32, i32],
+    "tasu_gemm_gate_up_plan": [i32, i32, i32, i32],
     "tasu_streamk_schedule": [i32, i32, i32, vp, vp, i32],
     "tasu_gemm_nt_bf16_streamk": [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i64, vp],
     "tasu_comm_available": [],
@@ -181,10 +182,10 @@ PROTOTYPES.update({
     "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 _lib = None
 
-GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")
+GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm_dispatch.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")
 
 
 def gemm_source_hash():

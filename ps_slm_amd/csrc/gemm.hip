@@ -18,8 +18,7 @@
 #include <utility>
 
 #include "common.h"
-#include "gemm_epilogue.h"
-#include "../../include/tasu_hip.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -286,249 +285,91 @@ int launch(GemmArgs a, hipStream_t st) {
   return TASU_OK;
 }
 
-int sched_variant() {
-  static const int v = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_SCHED");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-
 template <int OUT_MODE, bool HAS_BIAS>
 int launch_tiled(const GemmArgs& a, int bn, hipStream_t st) {
   if (bn == 256) return launch<256, 256, 2, 4, OUT_MODE, HAS_BIAS, 1>(a, st);
   if (bn == 192)
     return a.ksplit > 1 ? launch<256, 192, 2, 4, OUT_MODE, HAS_BIAS, 1, true>(a, st)
                         : launch<256, 192, 2, 4, OUT_MODE, HAS_BIAS, 1>(a, st);
-  if (sched_variant() == 1)
+  if (tasu_gemm::lab_switches().sched == 1)
     return bn == 96 ? launch<128, 96, 2, 2, OUT_MODE, HAS_BIAS, 1>(a, st) : launch<128, 128, 2, 2, OUT_MODE, HAS_BIAS, 1>(a, st);
   return bn == 96 ? launch<128, 96, 2, 2, OUT_MODE, HAS_BIAS, 0>(a, st) : launch<128, 128, 2, 2, OUT_MODE, HAS_BIAS, 0>(a, st);
 }
 
-// Tile choice: both configurations run 2 blocks per CU (512 slots on 256 CUs).  When the grid is at most two waves of
-// blocks, the tail efficiency tiles / (waves * 512) decides (N = 1536 at M = 4096: 384 tiles of 128x128 fill 75 % of
-// the slots, 512 tiles of 128x96 fill all of them: measured +11...+17 %); larger grids keep the wider tile, whose MFMA
-// per LDS read ratio is better (measured: N = 8960 loses 10 % with the narrow tile).
-int pick_bn(int M, int N) {
-  static const int forced = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_BN");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced == 96 || forced == 128 || forced == 192 || forced == 256) return forced;
-  // 256 x 256 (one block per CU): worth it when the grid is many rounds of 256 blocks, or (almost) exactly one round
-  // (measured on MI355X, M = 4096 / 8192: gate_up +15 %, lm_head +8 %, M = 8192 x N = 1536..2048 +10...18 %;
-  //  560- and 784-tile grids lose 2...3 % against the 128-wide tiles and stay there).
-  const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  if (t256 >= 1024 || (t256 >= 192 && t256 <= 256)) return 256;
-  const long slots = 512;
-  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128), t96 = (long)((M + 127) / 128) * ((N + 95) / 96);
-  const long w128 = (t128 + slots - 1) / slots, w96 = (t96 + slots - 1) / slots;
-  if (w128 > 2) return 128;
-  const double e128 = (double)t128 / (double)(w128 * slots), e96 = (double)t96 / (double)(w96 * slots) / 1.08;
-  return e96 > e128 ? 96 : 128;
-}
-
-// 0 = heuristic, 1 = always the 128-wide 2-blocks-per-CU kernel of this file, 2 = always gemm_pipe.hip
-int kernel_choice() {
-  static const int v = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_KERNEL");
-    if (!e) return 0;
-    return e[0] == 'p' ? 2 : (e[0] == 'v' ? 1 : 0);
-  }();
-  return v;
-}
-
-}  // namespace
-
-int tasu_gemm_pipe_dispatch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias,
-                            const float* resid, int M, int N, int K, int out_mode, int bn, hipStream_t st, int n0, int n1);
-int tasu_gemm_pp_dispatch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, const float* resid,
-                          int M, int N, int K, int out_mode, hipStream_t st, int n0, int n1, void* ws, size_t ws_bytes, double sk_rem);
-namespace tasu_pp {
-double sk_max_rem();
-int cu_count();
-}
-
-// Split-K plan for the 256 x 192 tile: ksplit blocks per tile so that tiles * ksplit is (close to) one round of 256
-// blocks, every split keeping >= 16 K-steps.  Returns 1 when the workspace is missing or too small.
-static int plan_ksplit(int M, int N, int K, size_t ws_bytes) {
-  static const int forced = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_KSPLIT");
-    return e ? atoi(e) : 0;
-  }();
-  const long tiles = (long)((M + 255) / 256) * ((N + 191) / 192);
-  int ks = forced > 0 ? forced : (int)(256 / tiles);
-  const int nk = K / BK;
-  if (ks > nk / 16) ks = nk / 16;
-  if (ks > 8) ks = 8;
-  if (ks < 1) ks = 1;
-  if (tiles > TASU_GEMM_WS_COUNTERS) return 1;
-  while (ks > 1 && TASU_GEMM_WS_COUNTERS * sizeof(int) + (size_t)tiles * ks * 256 * 192 * 4 > ws_bytes) --ks;
-  return ks;
-}
-
-// out_mode: TASU_GEMM_OUT_* or tasu_gemm::OUT_DSWIGLU (`resid` is then the saved gate|up matrix, bf16 [M, 2N], C = dgu [M, 2N]:
-// served by the gemm_pipe / gemm_pp kernels only -- kUnsupported otherwise, and tasu_gemm_dswiglu runs the two-kernel form)
-constexpr int kUnsupported = -1000;
-// plan (optional): the decision only -- *plan = one of TASU_GEMM_PLAN_* (include/tasu_hip.h), nothing is launched
-static int gemm_policy(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, const float* resid, int M,
-                       int N, int K, int out_mode, void* workspace, int64_t workspace_bytes, void* stream, int* plan = nullptr) {
-  const bool dsw = out_mode == tasu_gemm::OUT_DSWIGLU;
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return TASU_ERR_ARG;
-  if (K % BK != 0 || lda % 8 != 0 || ldb % 8 != 0) return TASU_ERR_ARG;
-  if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)workspace & 15)) return TASU_ERR_ARG;
-  if (out_mode == TASU_GEMM_OUT_F32_RESID_BF16R && !resid) return TASU_ERR_ARG;
-  GemmArgs a;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)B;
-  a.C = C;
-  a.R = resid;
-  a.bias = (const bf16*)bias;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.tiles_m = a.tiles_n = 0;
-  a.ksplit = 1;
-  a.partial = nullptr;
-  a.counters = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const bool hb = bias != nullptr;
-  const size_t ws_bytes = workspace ? (size_t)workspace_bytes : 0;
-  static const int forced_bn = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_BN");
-    return e ? atoi(e) : 0;
-  }();
-  // ---- kernel / tile policy (MI355X, cold weight operands as inside the training step; tools/bench_gemm.py --cold):
-  //  * the pipelined kernel with loader waves (gemm_pipe.hip; tiles 256 x 128, 128 x 192, 256 x 96) is the fastest on
-  //    every decoder, lm_head and projector shape (qkv 700 -> 822, gate_up 780 -> 837, d_down 690 -> 772, d_lm_head
-  //    975 -> 1149 TFLOP/s ...); the tile is the one that fills whole rounds of 256 one-per-CU blocks at the least cost;
-  //  * grids that cover less than half of the CUs behind K >= 16384 and too few K-tile pairs per CU for the stream-K schedule
-  //    (below) split K over the 256 x 192 tiles of this file instead (256 / 512 x 1536 x 17920: 130 / 150 us against 190 on
-  //    the loader-wave tiles; at K = 8960 the loader-wave tiles win: 1024 rows 94 against 162 us);
-  //  * problems of at most 64 rows keep the 128-row tiles of this file (128 x 1536 x 8960: 73 us on 256 x 96 tiles, 122 here).
-  static const bool pp_on = [] {
-    const char* e = tasu_lab_env("TASU_GEMM_PP");
-    return !(e && e[0] == '0');
-  }();
-  int use_pipe_bn = 0;
-  if (kernel_choice() == 2) {
-    use_pipe_bn = (forced_bn == 96 || forced_bn == 128 || forced_bn == 192) ? forced_bn : -1;
-  } else if (kernel_choice() == 0 && forced_bn == 0 && M > 64) {
-    use_pipe_bn = -1;
-  }
-  if (use_pipe_bn != 0) {
-    const long tm = (M + 255) / 256;
-    const long t128 = tm * ((N + 127) / 128), t96 = tm * ((N + 95) / 96);
-    const long t256 = tm * ((N + 255) / 256);
-    const int cus = tasu_pp::cu_count();
-    const bool sk = pp_on && kernel_choice() == 0 && K >= 256 && K % 128 == 0 &&
-                    tasu_gemm::sk_plan(t256, K / 128, cus, ws_bytes >= TASU_GEMM_WS_COUNTERS * sizeof(int) + (size_t)cus * 262144,
-                                       tasu_pp::sk_max_rem()) > 0;
-    if (!dsw && !sk && kernel_choice() == 0 && M > 128 && t96 < 128 && K >= 16384 && plan_ksplit(M, N, K, ws_bytes) > 1) {
-      use_pipe_bn = 0;                              // falls through to the split-K tile below
-    } else {
-      if (use_pipe_bn < 0) {
-        // time ~ rounds of one-block-per-CU grids x tile area / per-FLOP efficiency of the tile (8192^3, cold: 256 x 128
-        // 1300, 128 x 192 1123, 256 x 96 ~1040 TFLOP/s).  N = 1536 at M = 4096 -> 256 tiles of 128 x 192 (+7 % over
-        // 256 x 96: fewer staged bytes and fragment reads per FLOP); wide grids -> 256 x 128.
-        auto cost = [&](long tiles, double area, double eff) { return (double)((tiles + 255) / 256) * area / eff; };
-        const long t192 = (long)((M + 127) / 128) * ((N + 191) / 192);
-        const double c128 = cost(t128, 256.0 * 128, 1.00), c192 = cost(t192, 128.0 * 192, 0.86), c96 = cost(t96, 256.0 * 96, 0.80);
-        use_pipe_bn = c128 <= c192 && c128 <= c96 ? 128 : (c192 <= c96 ? 192 : 96);
-        // the 256 x 256 eight-wave kernel (gemm_pp.hip): 2/3 of the L2 -> LDS bytes per FLOP of the 256 x 128 tile.  Measured on
-        // whole rounds at K = 1536 (4096 x 16384: 1232 vs 995 TFLOP/s) its per-FLOP efficiency is 1.24 x that tile's, so it wins
-        // wherever its coarser rounds do not eat that up (gate|up, lm_head; d_down's 3 rounds against 5: a tie on paper, +0.5 %
-        // on the step measured with TASU_GEMM_PP_EFF = 1.26 against 1.19 on one box; not the one-round N = 1536 grids)
-        if (pp_on && kernel_choice() == 0 && K >= 256 && K % 128 == 0) {
-          static const double pp_eff = [] {            // TASU_GEMM_PP_EFF: tuning runs
-            const char* e = tasu_lab_env("TASU_GEMM_PP_EFF");
-            return e ? atof(e) : 1.26;
-          }();
-          // stream-K (gemm_pp.hip; needs the workspace): the 256 x 256 tiles fill FRACTIONAL rounds -- every workgroup gets the
-          // same number of K-tile pairs -- for the price of the partial tiles' round trip (~35 us per launch whatever K is:
-          // 1e8 / K in the units of this model).  That serves d_gate_up (96 tiles on 256 CUs, K = 17920: 203 -> 181 us); at
-          // K = 8960 (down) the 128 x 192 one-round grid still wins (100 vs 108 us).
-          const double c256_whole = cost(t256, 256.0 * 256, pp_eff);
-          const double c256_sk = sk ? (double)t256 / cus * 256.0 * 256 / pp_eff + 1.0e8 / K : 1e30;
-          const double c256 = c256_sk < c256_whole ? c256_sk : c256_whole;
-          const double best = use_pipe_bn == 128 ? c128 : (use_pipe_bn == 192 ? c192 : c96);
-          if (c256 < best) {
-            if (c256_sk < c256_whole) {
-              if (plan) return *plan = TASU_GEMM_PLAN_PP256_STREAMK, TASU_OK;
-              return tasu_gemm_pp_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, st, 0, 0, workspace, ws_bytes, -2.0);
-            }
-            // a mostly empty last round of big tiles (d_down: 560 tiles = 2.19 rounds): whole rounds on the big tiles, the
-            // remaining columns on the small tiles in a second launch (TASU_GEMM_NSPLIT=0 disables)
-            static const bool split_on = [] {
-              const char* e = tasu_lab_env("TASU_GEMM_NSPLIT");
-              return !(e && e[0] == '0');
-            }();
-            const long tn = (N + 255) / 256, full = (tm * tn) / 256, tn_main = full * 256 / tm;
-            if (split_on && full >= 1 && tn_main > 0 && tn_main < tn) {
-              const int n_main = (int)tn_main * 256, n_tail = N - n_main;
-              const long u128 = tm * ((n_tail + 127) / 128), u192 = (long)((M + 127) / 128) * ((n_tail + 191) / 192);
-              const double t128 = cost(u128, 256.0 * 128, 1.00), t192 = cost(u192, 128.0 * 192, 0.86);
-              const double c_split = (double)full * 256.0 * 256 / pp_eff + (t128 < t192 ? t128 : t192) + 0.05 * 256.0 * 256;
-              if (c_split < c256) {
-                if (plan) return *plan = t128 < t192 ? TASU_GEMM_PLAN_PP256_PLUS_PIPE128 : TASU_GEMM_PLAN_PP256_PLUS_PIPE192, TASU_OK;
-                const int rc = tasu_gemm_pp_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, st, 0, n_main, nullptr, 0, -2.0);
-                if (rc) return rc;
-                return tasu_gemm_pipe_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, t128 < t192 ? 128 : 192, st,
-                                               n_main, 0);
-              }
-            }
-            if (plan) return *plan = TASU_GEMM_PLAN_PP256, TASU_OK;
-            return tasu_gemm_pp_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, st, 0, 0, nullptr, 0, -2.0);
-          }
-        }
-      }
-      if (plan) return *plan = use_pipe_bn == 128 ? TASU_GEMM_PLAN_PIPE128 : (use_pipe_bn == 192 ? TASU_GEMM_PLAN_PIPE192 : TASU_GEMM_PLAN_PIPE96), TASU_OK;
-      return tasu_gemm_pipe_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, use_pipe_bn, st, 0, 0);
+// Launches what plan_nt (gemm_dispatch.h) decided for the problem in `a` (make_args; a.relu is the one epilogue option here and
+// reaches the gemm_pipe / gemm_pp kernels only).  workspace: that of tasu_gemm_nt_bf16_ws, or nullptr.
+int run_nt(const tasu_gemm::Plan& p, const tasu_gemm::Args& a, int out_mode, void* workspace, size_t ws_bytes, hipStream_t st) {
+  switch (p.kind) {
+    case TASU_GEMM_PLAN_PP256:
+    case TASU_GEMM_PLAN_PP256_STREAMK:
+      return tasu_gemm_pp_dispatch(a, out_mode, st, p.streamk ? workspace : nullptr, p.streamk ? ws_bytes : 0, p.sk_rem);
+    case TASU_GEMM_PLAN_PP256_PLUS_PIPE128:
+    case TASU_GEMM_PLAN_PP256_PLUS_PIPE192: {
+      tasu_gemm::Args main = a, tail = a;
+      main.n1 = tail.n0 = p.n_main;
+      const int rc = tasu_gemm_pp_dispatch(main, out_mode, st, nullptr, 0, p.sk_rem);
+      return rc ? rc : tasu_gemm_pipe_dispatch(tail, out_mode, p.bn, st);
     }
+    case TASU_GEMM_PLAN_PIPE128:
+    case TASU_GEMM_PLAN_PIPE192:
+    case TASU_GEMM_PLAN_PIPE96:
+      return tasu_gemm_pipe_dispatch(a, out_mode, p.bn, st);
+    case TASU_GEMM_PLAN_TILE192_SPLITK:
+    case TASU_GEMM_PLAN_TILES:
+      break;
+    default:
+      return TASU_ERR_ARG;
   }
-  if (dsw) return kUnsupported;
-  int bn;
-  if (kernel_choice() == 0 && forced_bn == 0 && M > 128) {
-    bn = 192;                                       // the deep small-grid case above
-  } else {
-    bn = pick_bn(M, N);
+  GemmArgs g{a.A, a.B, a.C, a.R, a.bias, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, 0, 0, p.ksplit, nullptr, nullptr};
+  if (p.ksplit > 1) {
+    g.counters = (int*)workspace;
+    g.partial = (float*)((char*)workspace + TASU_GEMM_WS_COUNTERS * sizeof(int));
   }
-  if (bn == 192) {
-    a.ksplit = plan_ksplit(M, N, K, ws_bytes);
-    if (a.ksplit > 1) {
-      a.counters = (int*)workspace;
-      a.partial = (float*)((char*)workspace + TASU_GEMM_WS_COUNTERS * sizeof(int));
-    }
-  }
-  if (plan) return *plan = a.ksplit > 1 ? TASU_GEMM_PLAN_TILE192_SPLITK : TASU_GEMM_PLAN_TILES, TASU_OK;
+  const bool hb = a.bias != nullptr;
   switch (out_mode) {
     case TASU_GEMM_OUT_BF16:
-      return hb ? launch_tiled<TASU_GEMM_OUT_BF16, true>(a, bn, st) : launch_tiled<TASU_GEMM_OUT_BF16, false>(a, bn, st);
+      return hb ? launch_tiled<TASU_GEMM_OUT_BF16, true>(g, p.bn, st) : launch_tiled<TASU_GEMM_OUT_BF16, false>(g, p.bn, st);
     case TASU_GEMM_OUT_F32:
-      return hb ? launch_tiled<TASU_GEMM_OUT_F32, true>(a, bn, st) : launch_tiled<TASU_GEMM_OUT_F32, false>(a, bn, st);
+      return hb ? launch_tiled<TASU_GEMM_OUT_F32, true>(g, p.bn, st) : launch_tiled<TASU_GEMM_OUT_F32, false>(g, p.bn, st);
     case TASU_GEMM_OUT_F32_RESID_BF16R:
-      return hb ? launch_tiled<TASU_GEMM_OUT_F32_RESID_BF16R, true>(a, bn, st)
-                : launch_tiled<TASU_GEMM_OUT_F32_RESID_BF16R, false>(a, bn, st);
+      return hb ? launch_tiled<TASU_GEMM_OUT_F32_RESID_BF16R, true>(g, p.bn, st)
+                : launch_tiled<TASU_GEMM_OUT_F32_RESID_BF16R, false>(g, p.bn, st);
     default:
       return TASU_ERR_ARG;
   }
 }
 
+// The pointer half of the contract of tasu_gemm_nt_bf16_ws (the shape half is plan_nt's)
+int check_operands(const void* A, int lda, const void* B, int ldb, const void* C, const float* resid, int out_mode, const void* workspace) {
+  if (!A || !B || !C || lda % 8 != 0 || ldb % 8 != 0) return TASU_ERR_ARG;
+  if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)workspace & 15)) return TASU_ERR_ARG;
+  if (out_mode == TASU_GEMM_OUT_F32_RESID_BF16R && !resid) return TASU_ERR_ARG;
+  return TASU_OK;
+}
+
+// Plan, then launch the plan.  out_mode: TASU_GEMM_OUT_* or tasu_gemm::OUT_DSWIGLU (`resid` is then the saved gate|up matrix, bf16
+// [M, 2N], C = dgu [M, 2N]; kUnsupported where the plan is not a gemm_pipe / gemm_pp kernel, and tasu_gemm_dswiglu runs the two-kernel
+// form).  relu_fused (optional): the caller wants C = bf16(max(acc + bias, 0)); set to whether the plan's kernels do that in their
+// epilogue (those of gemm_pipe / gemm_pp) or the caller has to (the tiles of this file).
+int gemm_policy(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, const float* resid, int M, int N, int K,
+                int out_mode, void* workspace, int64_t workspace_bytes, void* stream, bool* relu_fused = nullptr) {
+  int rc = check_operands(A, lda, B, ldb, C, resid, out_mode, workspace);
+  if (rc) return rc;
+  const size_t ws_bytes = workspace ? (size_t)workspace_bytes : 0;
+  tasu_gemm::Plan p;
+  rc = tasu_gemm::plan_nt(M, N, K, out_mode, ws_bytes, tasu_pp::cu_count(), tasu_gemm::lab_switches(), &p);
+  if (rc) return rc;
+  tasu_gemm::Args a = tasu_gemm::make_args(A, lda, B, ldb, C, ldc, bias, resid, M, N, K);
+  if (relu_fused) a.relu = *relu_fused = p.kind != TASU_GEMM_PLAN_TILES && p.kind != TASU_GEMM_PLAN_TILE192_SPLITK;
+  return run_nt(p, a, out_mode, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+}  // namespace
+
 namespace tasu_gemm {
 long long& gemm_launches() {
   static long long n = 0;
   return n;
-}
-int& relu_next() {
-  static thread_local int flag = 0;
-  return flag;
-}
-int& act_ld_next() {
-  static int v = 0;
-  return v;
 }
 }  // namespace tasu_gemm
 
@@ -540,13 +381,8 @@ extern "C" int tasu_relu_fwd(const void* x, void* y, int64_t n, void* stream);
 // of gemm.hip serve (at most 128 rows) run the GEMM and tasu_relu_fwd in place.
 extern "C" int tasu_gemm_bias_relu_bf16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, int M, int N,
                                         int K, void* workspace, int64_t workspace_bytes, void* stream) {
-  int plan = 0;
-  int rc = gemm_policy(A, lda, B, ldb, C, ldc, bias, nullptr, M, N, K, TASU_GEMM_OUT_BF16, workspace, workspace_bytes, stream, &plan);
-  if (rc) return rc;
-  const bool fused = plan != TASU_GEMM_PLAN_TILES && plan != TASU_GEMM_PLAN_TILE192_SPLITK;
-  tasu_gemm::relu_next() = fused ? 1 : 0;
-  rc = gemm_policy(A, lda, B, ldb, C, ldc, bias, nullptr, M, N, K, TASU_GEMM_OUT_BF16, workspace, workspace_bytes, stream);
-  tasu_gemm::relu_next() = 0;
+  bool fused = false;
+  const int rc = gemm_policy(A, lda, B, ldb, C, ldc, bias, nullptr, M, N, K, TASU_GEMM_OUT_BF16, workspace, workspace_bytes, stream, &fused);
   if (rc || fused) return rc;
   if (ldc != N) return TASU_ERR_ARG;                       // (the in-place ReLU walks a dense matrix)
   return tasu_relu_fwd(C, C, (int64_t)M * N, stream);
@@ -562,11 +398,10 @@ extern "C" int tasu_gemm_nt_bf16_ws(const void* A, int lda, const void* B, int l
 // The dispatcher's decision for a problem, without launching anything (no GPU needed; include/tasu_hip.h)
 extern "C" int tasu_gemm_plan(int M, int N, int K, int out_mode, int with_workspace) {
   if (out_mode != TASU_GEMM_OUT_BF16 && out_mode != TASU_GEMM_OUT_F32 && out_mode != TASU_GEMM_OUT_F32_RESID_BF16R) return -1;
-  alignas(16) static char dummy[16];
-  int plan = -1;
-  const int rc = gemm_policy(dummy, K, dummy, K, dummy, N, nullptr, (const float*)dummy, M, N, K, out_mode, with_workspace ? dummy : nullptr,
-                             with_workspace ? ((int64_t)64 << 20) + 16384 : 0, nullptr, &plan);
-  return rc == TASU_OK ? plan : -1;
+  tasu_gemm::Plan p;
+  const int rc = tasu_gemm::plan_nt(M, N, K, out_mode, with_workspace ? ((size_t)64 << 20) + 16384 : 0, tasu_pp::cu_count(),
+                                    tasu_gemm::lab_switches(), &p);
+  return rc == TASU_OK ? p.kind : -1;
 }
 
 extern "C" int tasu_swiglu_bwd(const void* dact, const void* gu, void* dgu, int M, int I, void* stream);
@@ -585,7 +420,7 @@ extern "C" int tasu_gemm_dswiglu(const void* dy, int lddy, const void* WdT, int 
   if (fused_env && fused_env[0] == '1') {
     const int rc = gemm_policy(dy, lddy, WdT, ldw, dgu, 2 * I, nullptr, (const float*)gu, M, I, K, tasu_gemm::OUT_DSWIGLU, workspace,
                                workspace_bytes, stream);
-    if (rc != kUnsupported) return rc;
+    if (rc != tasu_gemm::kUnsupported) return rc;
   }
 #endif
   if (!dact_ws || ((uintptr_t)dact_ws & 15)) return TASU_ERR_ARG;

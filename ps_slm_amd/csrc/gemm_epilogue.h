@@ -49,10 +49,6 @@ struct Args {
 // launches behind its GEMM CALLS -- a column-split call is two -- so that roofline.avg_launch_us is per kernel launch, the unit
 // rocprofv3's per-kernel average has)
 long long& gemm_launches();
-// set by tasu_gemm_bias_relu_bf16 around its call of the dispatcher (host; the dispatchers copy it into Args::relu)
-int& relu_next();
-// likewise for tasu_gemm_gate_up_swiglu_ld: the act leading dimension of the next gate|up launch (0 = I)
-int& act_ld_next();
 
 // The work-item list of a workgroup of the 256 x 256 kernel (gemm_pp.hip), as one piece of host / device code so that the
 // schedule can be checked on the CPU (tasu_streamk_schedule, tests/test_cabi.py).  Whole tiles (and K-range slabs) are dealt

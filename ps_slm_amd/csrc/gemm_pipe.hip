@@ -23,7 +23,7 @@
 // at chunk c ^ ((r>>1)&7)) is applied on the per-lane SOURCE offset and again on the ds_read_b128 address.
 #include <stdlib.h>
 
-#include "gemm_epilogue.h"
+#include "gemm_dispatch.h"
 
 namespace tasu_pipe {
 
@@ -270,18 +270,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pipe_kernel(Args p) {
   }
 }
 
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    }
-    return cus >= 8 ? (cus & ~7) : 8;              // a multiple of 8 keeps a workgroup's tiles on one XCD
-  }();
-  return n;
-}
-
 template <int BM, int BN, int OUT_MODE, bool HAS_BIAS>
 int launch(Args a, hipStream_t st) {
   constexpr int LDS = ring_slots(BM, BN) * (BM + BN) * BK * 2;
@@ -295,7 +283,7 @@ int launch(Args a, hipStream_t st) {
   const int n_end = a.n1 > 0 ? a.n1 : a.N;
   a.tiles_n = OUT_MODE == OUT_GU_SWIGLU ? (n_end - a.n0 + 63) / 64 : (n_end - a.n0 + BN - 1) / BN;
   const int ntiles = a.tiles_m * a.tiles_n * a.ksplit;
-  const int grid = ntiles < cu_count() ? ntiles : cu_count();
+  const int grid = ntiles < tasu_pp::cu_count() ? ntiles : tasu_pp::cu_count();
   ++tasu_gemm::gemm_launches();
   TASU_LAUNCH((gemm_pipe_kernel<BM, BN, OUT_MODE, HAS_BIAS>), dim3(grid), dim3(512), LDS, st, a);
   return TASU_OK;
@@ -310,30 +298,10 @@ int launch_bn(const Args& a, int bn, hipStream_t st) {
 
 }  // namespace tasu_pipe
 
-// called from gemm.hip's dispatcher
-int tasu_gemm_pipe_dispatch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias,
-                            const float* resid, int M, int N, int K, int out_mode, int bn, hipStream_t st, int n0, int n1) {
+int tasu_gemm_pipe_dispatch(tasu_gemm::Args a, int out_mode, int bn, hipStream_t st) {
   using namespace tasu_pipe;
-  Args a;
-  a.n0 = n0;
-  a.n1 = n1;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)B;
-  a.C = C;
-  a.R = resid;
-  a.bias = (const bf16*)bias;
-  a.relu = out_mode == TASU_GEMM_OUT_BF16 ? tasu_gemm::relu_next() : 0;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.tiles_m = a.tiles_n = 0;
-  a.act = nullptr;
-  a.ksplit = 1;
-  a.split_stride = 0;
-  const bool hb = bias != nullptr;
+  if (out_mode != TASU_GEMM_OUT_BF16) a.relu = 0;
+  const bool hb = a.bias != nullptr;
   switch (out_mode) {
     case TASU_GEMM_OUT_BF16:
       return hb ? launch_bn<TASU_GEMM_OUT_BF16, true>(a, bn, st) : launch_bn<TASU_GEMM_OUT_BF16, false>(a, bn, st);
@@ -343,9 +311,9 @@ int tasu_gemm_pipe_dispatch(const void* A, int lda, const void* B, int ldb, void
       return hb ? launch_bn<TASU_GEMM_OUT_F32_RESID_BF16R, true>(a, bn, st)
                 : launch_bn<TASU_GEMM_OUT_F32_RESID_BF16R, false>(a, bn, st);
 #ifdef TASU_LAB
-    case OUT_DSWIGLU:                                // `resid` = the saved gate|up matrix (bf16 [M, 2N]); C = dgu [M, 2N]
-      if (hb || !resid || N % 8 || ldc != 2 * N || bn == 96) return TASU_ERR_ARG;
-      a.act = (bf16*)resid;
+    case OUT_DSWIGLU:                                // a.R = the saved gate|up matrix (bf16 [M, 2N]); C = dgu [M, 2N]
+      if (hb || !a.R || a.N % 8 || a.ldc != 2 * a.N || bn == 96) return TASU_ERR_ARG;
+      a.act = (bf16*)a.R;
       a.R = nullptr;
       return launch_bn<OUT_DSWIGLU, false>(a, bn, st);
 #endif
@@ -354,101 +322,54 @@ int tasu_gemm_pipe_dispatch(const void* A, int lda, const void* B, int ldb, void
   }
 }
 
-int tasu_gemm_pp_gu_dispatch(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int M, int I, int K, hipStream_t st,
-                             int n0, int n1, void* ws, size_t ws_bytes);
-namespace tasu_pp {
-double sk_max_rem();
-}
-
+// gate|up + SwiGLU: plan_gate_up (gemm_dispatch.h) decides, this launches the plan.  ld_act: leading dimension of act (0 = I).
 // workspace (that of tasu_gemm_nt_bf16_ws) or nullptr: with it the 256 x 256 kernel may cut its last rounds along K (stream-K)
-extern "C" int tasu_gemm_gate_up_swiglu_ws(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int M, int I,
-                                           int K, void* workspace, int64_t workspace_bytes, void* stream) {
+static int gate_up_swiglu(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int ld_act, int M, int I, int K,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace tasu_pipe;
   if (((uintptr_t)workspace & 15) || workspace_bytes < 0) return TASU_ERR_ARG;
-  void* const ws = workspace;
   const size_t ws_bytes = workspace ? (size_t)workspace_bytes : 0;
-  if (!A || !Wgu || !gu || !act || M <= 0 || I <= 0 || I % 4 || K <= 0 || K % BK || lda % 8 || ldw % 8) return TASU_ERR_ARG;
+  if (!A || !Wgu || !gu || !act || lda % 8 || ldw % 8) return TASU_ERR_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)Wgu & 15) || ((uintptr_t)gu & 7) || ((uintptr_t)act & 7)) return TASU_ERR_ARG;
-  static const int forced = [] {                  // TASU_GEMM_GU_KERNEL=pipe|pp: A/B runs and tests of either kernel
-    const char* e = tasu_lab_env("TASU_GEMM_GU_KERNEL");
-    return !e ? 0 : (e[0] == 'p' && e[1] == 'p' ? 2 : 1);
-  }();
-  auto pipe_range = [&](int n0) {                 // 256 x 128 tiles (64 act columns) of this file over act columns [n0, I)
-    Args a;
-    a.A = (const bf16*)A;
-    a.B = (const bf16*)Wgu;
-    a.C = gu;
-    a.R = nullptr;
-    a.bias = nullptr;
-    a.M = M;
-    a.N = I;
-    a.K = K;
-    a.lda = lda;
-    a.ldb = ldw;
-    a.ldc = 2 * I;
-    a.tiles_m = a.tiles_n = 0;
-    a.act = (bf16*)act;
-    a.act_ld = tasu_gemm::act_ld_next();
-    a.ksplit = 1;
-    a.split_stride = 0;
-    a.n0 = n0;
-    return launch<256, 128, OUT_GU_SWIGLU, false>(a, (hipStream_t)stream);
-  };
-  const bool pp_ok = I % 128 == 0 && K >= 256 && K % 128 == 0;
-  if (forced == 2 && pp_ok) return tasu_gemm_pp_gu_dispatch(A, lda, Wgu, ldw, gu, act, M, I, K, (hipStream_t)stream, 0, 0, ws, ws_bytes);
-  if (forced == 0 && pp_ok) {
-    // tile policy as in tasu_gemm_nt_bf16_ws (gemm.hip): 256 x 256 tiles (128 act columns, gemm_pp.hip) where their coarser
-    // rounds cost less than the per-FLOP efficiency they bring (4096 x 17920 x 1536: 257 -> 218 us); and when the last round
-    // of big tiles would be mostly empty (1120 tiles on 256 CUs: 4.375 rounds), whole rounds on the big tiles + the remaining
-    // columns on the small ones in a second launch (4 rounds + 192 tiles of 256 x 128)
-    static const bool pp_on = [] {
-      const char* e = tasu_lab_env("TASU_GEMM_PP");
-      return !(e && e[0] == '0');
-    }();
-    static const bool split_on = [] {
-      const char* e = tasu_lab_env("TASU_GEMM_NSPLIT");
-      return !(e && e[0] == '0');
-    }();
-    const long tm = (M + 255) / 256, cus = cu_count(), tn = (I + 127) / 128;
-    auto rounds = [&](long tiles) { return (double)((tiles + cus - 1) / cus); };
-    const double c128 = rounds(tm * ((I + 63) / 64)) * 0.5;
-    // stream-K (workspace given): the big tiles fill fractional rounds, for the price of the partial tiles' round trip (~35 us)
-    const bool sk = tasu_gemm::sk_plan(tm * tn, K / 128, (int)cus, ws_bytes >= TASU_GEMM_WS_COUNTERS * sizeof(int) + (size_t)cus * 262144,
-                                       tasu_pp::sk_max_rem()) > 0;
-    const double c256_whole = rounds(tm * tn) / 1.26;
-    const double c256_sk = sk ? ((double)(tm * tn) / cus) / 1.26 + 1.0e8 / K / 52012.0 : 1e30;
-    const double c256 = c256_sk < c256_whole ? c256_sk : c256_whole;
-    if (pp_on && c256 < c128) {
-      if (c256_sk < c256_whole)
-        return tasu_gemm_pp_gu_dispatch(A, lda, Wgu, ldw, gu, act, M, I, K, (hipStream_t)stream, 0, 0, ws, ws_bytes);
-      const long full = (tm * tn) / cus;                          // whole rounds of big tiles
-      const long tn_main = full * cus / tm;                       // column tiles they cover
-      if (split_on && full >= 1 && tn_main < tn && tn_main > 0) {
-        const double c_split = (double)full / 1.26 + rounds(tm * (tn - tn_main) * 2) * 0.5 + 0.05;   // + the second launch's ramp
-        if (c_split < c256) {
-          const int rc = tasu_gemm_pp_gu_dispatch(A, lda, Wgu, ldw, gu, act, M, I, K, (hipStream_t)stream, 0, (int)tn_main * 128, nullptr, 0);
-          return rc ? rc : pipe_range((int)tn_main * 128);
-        }
-      }
-      return tasu_gemm_pp_gu_dispatch(A, lda, Wgu, ldw, gu, act, M, I, K, (hipStream_t)stream, 0, 0, nullptr, 0);
-    }
+  Plan p;
+  int rc = plan_gate_up(M, I, K, ws_bytes, tasu_pp::cu_count(), lab_switches(), &p);
+  if (rc) return rc;
+  Args a = make_args(A, lda, Wgu, ldw, gu, 2 * I, nullptr, nullptr, M, I, K);
+  a.act = (bf16*)act;
+  a.act_ld = ld_act;
+  if (p.kind != TASU_GEMM_GU_PLAN_PIPE) {           // 256 x 256 tiles (128 act columns, gemm_pp.hip) over act columns [0, n_main)
+    a.n1 = p.n_main;
+    rc = tasu_gemm_pp_gu_dispatch(a, (hipStream_t)stream, p.streamk ? workspace : nullptr, p.streamk ? ws_bytes : 0);
+    if (rc || p.kind != TASU_GEMM_GU_PLAN_PP_PLUS_PIPE) return rc;
+    a.n1 = 0;
   }
-  return pipe_range(0);
+  a.n0 = p.n_main;                                  // 256 x 128 tiles (64 act columns) of this file over act columns [n_main, I)
+  return launch<256, 128, OUT_GU_SWIGLU, false>(a, (hipStream_t)stream);
+}
+
+extern "C" int tasu_gemm_gate_up_swiglu_ws(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int M, int I,
+                                           int K, void* workspace, int64_t workspace_bytes, void* stream) {
+  return gate_up_swiglu(A, lda, Wgu, ldw, gu, act, 0, M, I, K, workspace, workspace_bytes, stream);
+}
+
+// What tasu_gemm_gate_up_swiglu_ws launches for a problem, without launching anything (no GPU needed; include/tasu_hip.h)
+extern "C" int tasu_gemm_gate_up_plan(int M, int I, int K, int with_workspace) {
+  tasu_gemm::Plan p;
+  const int rc = tasu_gemm::plan_gate_up(M, I, K, with_workspace ? ((size_t)64 << 20) + 16384 : 0, tasu_pp::cu_count(),
+                                         tasu_gemm::lab_switches(), &p);
+  return rc == TASU_OK ? p.kind : -1;
 }
 
 // act with a leading dimension (the LoRA recipe keeps [act | rank activations] side by side as the down projection's operand)
 extern "C" int tasu_gemm_gate_up_swiglu_ld(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int ld_act, int M,
                                            int I, int K, void* workspace, int64_t workspace_bytes, void* stream) {
   if (ld_act < I || ld_act % 8) return TASU_ERR_ARG;
-  tasu_gemm::act_ld_next() = ld_act == I ? 0 : ld_act;
-  const int rc = tasu_gemm_gate_up_swiglu_ws(A, lda, Wgu, ldw, gu, act, M, I, K, workspace, workspace_bytes, stream);
-  tasu_gemm::act_ld_next() = 0;
-  return rc;
+  return gate_up_swiglu(A, lda, Wgu, ldw, gu, act, ld_act == I ? 0 : ld_act, M, I, K, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tasu_gemm_gate_up_swiglu(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int M, int I,
                                         int K, void* stream) {
-  return tasu_gemm_gate_up_swiglu_ws(A, lda, Wgu, ldw, gu, act, M, I, K, nullptr, 0, stream);
+  return gate_up_swiglu(A, lda, Wgu, ldw, gu, act, 0, M, I, K, nullptr, 0, stream);
 }
 
 // q|k|v projection + bias + rotary embedding of the q and k heads in one launch (include/tasu_hip.h): 256 x 128 tiles, one
@@ -473,21 +394,8 @@ extern "C" int tasu_gemm_qkv_rope(const void* A, int lda, const void* Wqkv, int 
                                         stream);
     return rc ? rc : tasu_rope_fwd(qkv, cos_tab, sin_tab, nullptr, nullptr, nullptr, 1, M, H, G, stream);
   }
-  Args a;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)Wqkv;
-  a.C = qkv;
-  a.R = cos_tab;
-  a.bias = (const bf16*)bias;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldw;
-  a.ldc = N;
-  a.tiles_m = a.tiles_n = 0;
+  Args a = make_args(A, lda, Wqkv, ldw, qkv, N, bias, cos_tab, M, N, K);
   a.act = (bf16*)sin_tab;
-  a.ksplit = 1;
   a.split_stride = (long long)(H + G) * 128;       // first column that is not rotated (the v heads)
   return launch<256, 128, OUT_QKV_ROPE, false>(a, (hipStream_t)stream);
 }
@@ -502,20 +410,7 @@ extern "C" int tasu_gemm_nt_bf16_splitk(const void* A, int lda, const void* B, i
     return TASU_ERR_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)partials & 15)) return TASU_ERR_ARG;
   if ((((size_t)K / ksplit) * 2) % 16) return TASU_ERR_ARG;     // every K range starts 16-byte aligned
-  Args a;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)B;
-  a.C = partials;
-  a.R = nullptr;
-  a.bias = nullptr;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.tiles_m = a.tiles_n = 0;
-  a.act = nullptr;
+  Args a = make_args(A, lda, B, ldb, partials, ldc, nullptr, nullptr, M, N, K);
   a.ksplit = ksplit;
   a.split_stride = (long long)M * ldc;
   return launch<128, 192, TASU_GEMM_OUT_F32, false>(a, (hipStream_t)stream);

@@ -27,7 +27,7 @@
 //   its first read, so "the unit the NEXT phase reads has landed" is always "all but my 10 youngest DMAs are done".
 // The stream of K-tiles does not stop at tile boundaries (persistent workgroups, static tile list): the first units of a
 // workgroup's next tile land while it converts and stores the finished one.
-#include "gemm_epilogue.h"
+#include "gemm_dispatch.h"
 
 namespace tasu_pp {
 
@@ -412,20 +412,6 @@ int cu_count() {
   return n;
 }
 
-// Library default of sk_plan's max_rem.  Measured (profiles/r03_gemm_streamk.txt): the round trip of the partial tiles costs
-// ~35 us per launch; it pays for fewer tiles than CUs behind a long K (d_gate_up: 96 tiles, K = 17920: 203 -> 181 us), not for
-// shapes that only lose a fraction of their last round (d_down 2.19 rounds, gate|up 4.4, lm_head 18.6: slower by 5-25 us) --
-// so those keep whole tiles unless TASU_GEMM_SK_MAXREM says otherwise.  TASU_GEMM_SK=0 disables the schedule altogether.
-double sk_max_rem() {
-  static const double v = [] {
-    const char* off = tasu_lab_env("TASU_GEMM_SK");
-    if (off && off[0] == '0') return -1.0;
-    const char* e = tasu_lab_env("TASU_GEMM_SK_MAXREM");
-    return e ? atof(e) : 0.0;
-  }();
-  return v;
-}
-
 template <int OUT_MODE, bool HAS_BIAS>
 int launch(Args a, hipStream_t st) {
   constexpr int LDS = 2 * BUF;
@@ -440,7 +426,7 @@ int launch(Args a, hipStream_t st) {
   const int ntiles = a.tiles_m * a.tiles_n * a.ksplit;
   const int G = cu_count();
   // stream-K over the last (partial + one whole) round when the workspace is there (sk_plan, gemm_epilogue.h)
-  a.sk_tiles = a.ksplit == 1 && (long long)ntiles * (a.K / 128) < (1 << 22) ? sk_plan(ntiles, a.K / 128, G, a.sk_flags && a.sk_partial, a.sk_rem > -1.5 ? a.sk_rem : sk_max_rem()) : 0;
+  a.sk_tiles = a.ksplit == 1 && (long long)ntiles * (a.K / 128) < (1 << 22) ? sk_plan(ntiles, a.K / 128, G, a.sk_flags && a.sk_partial, a.sk_rem > -1.5 ? a.sk_rem : lab_switches().sk_max_rem) : 0;
   if (!a.sk_tiles) a.sk_flags = nullptr, a.sk_partial = nullptr;
   const int grid = a.sk_tiles || ntiles >= G ? G : ntiles;
   ++tasu_gemm::gemm_launches();
@@ -460,31 +446,12 @@ void set_sk_workspace(Args& a, void* ws, size_t ws_bytes, double sk_rem) {
 }  // namespace tasu_pp
 
 // C[M,N] = A[M,K] . B[N,K]^T (+ bias) with the 256 x 256 ping-pong kernel; same contract as tasu_gemm_nt_bf16_ws
-// (K % 64 == 0, lda / ldb % 8 == 0, 16-byte aligned operands).  Called from gemm.hip's dispatcher.
-int tasu_gemm_pp_dispatch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias, const float* resid,
-                          int M, int N, int K, int out_mode, hipStream_t st, int n0, int n1, void* ws, size_t ws_bytes, double sk_rem) {
+// (K % 64 == 0, lda / ldb % 8 == 0, 16-byte aligned operands).  Called from gemm.hip's run_nt.
+int tasu_gemm_pp_dispatch(tasu_gemm::Args a, int out_mode, hipStream_t st, void* ws, size_t ws_bytes, double sk_rem) {
   using namespace tasu_pp;
-  Args a;
   set_sk_workspace(a, ws, ws_bytes, sk_rem);
-  a.n0 = n0;
-  a.n1 = n1;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)B;
-  a.C = C;
-  a.R = resid;
-  a.bias = (const bf16*)bias;
-  a.relu = out_mode == TASU_GEMM_OUT_BF16 ? tasu_gemm::relu_next() : 0;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.tiles_m = a.tiles_n = 0;
-  a.act = nullptr;
-  a.ksplit = 1;
-  a.split_stride = 0;
-  const bool hb = bias != nullptr;
+  if (out_mode != TASU_GEMM_OUT_BF16) a.relu = 0;
+  const bool hb = a.bias != nullptr;
   switch (out_mode) {
     case TASU_GEMM_OUT_BF16:
       return hb ? launch<TASU_GEMM_OUT_BF16, true>(a, st) : launch<TASU_GEMM_OUT_BF16, false>(a, st);
@@ -493,9 +460,9 @@ int tasu_gemm_pp_dispatch(const void* A, int lda, const void* B, int ldb, void* 
     case TASU_GEMM_OUT_F32_RESID_BF16R:
       return hb ? launch<TASU_GEMM_OUT_F32_RESID_BF16R, true>(a, st) : launch<TASU_GEMM_OUT_F32_RESID_BF16R, false>(a, st);
 #ifdef TASU_LAB
-    case OUT_DSWIGLU:                                // `resid` = the saved gate|up matrix (bf16 [M, 2N]); C = dgu [M, 2N]
-      if (hb || !resid || N % 8 || ldc != 2 * N) return TASU_ERR_ARG;
-      a.act = (bf16*)resid;
+    case OUT_DSWIGLU:                                // a.R = the saved gate|up matrix (bf16 [M, 2N]); C = dgu [M, 2N]
+      if (hb || !a.R || a.N % 8 || a.ldc != 2 * a.N) return TASU_ERR_ARG;
+      a.act = (bf16*)a.R;
       a.R = nullptr;
       return launch<OUT_DSWIGLU, false>(a, st);
 #endif
@@ -504,31 +471,11 @@ int tasu_gemm_pp_dispatch(const void* A, int lda, const void* B, int ldb, void* 
   }
 }
 
-// gate|up projection + SwiGLU epilogue on 256 x 256 tiles (128 act columns); called from tasu_gemm_gate_up_swiglu (gemm_pipe.hip)
-int tasu_gemm_pp_gu_dispatch(const void* A, int lda, const void* Wgu, int ldw, void* gu, void* act, int M, int I, int K, hipStream_t st,
-                             int n0, int n1, void* ws, size_t ws_bytes) {
+// gate|up projection + SwiGLU epilogue on 256 x 256 tiles (128 act columns); called from the gate|up entry point (gemm_pipe.hip)
+int tasu_gemm_pp_gu_dispatch(tasu_gemm::Args a, hipStream_t st, void* ws, size_t ws_bytes) {
   using namespace tasu_pp;
-  if (I % 128 || K < 256 || K % 128) return TASU_ERR_ARG;
-  Args a;
+  if (a.N % 128 || a.K < 256 || a.K % 128) return TASU_ERR_ARG;
   set_sk_workspace(a, ws, ws_bytes, -2.0);
-  a.n0 = n0;
-  a.n1 = n1;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)Wgu;
-  a.C = gu;
-  a.R = nullptr;
-  a.bias = nullptr;
-  a.M = M;
-  a.N = I;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldw;
-  a.ldc = 2 * I;
-  a.tiles_m = a.tiles_n = 0;
-  a.act = (bf16*)act;
-  a.act_ld = tasu_gemm::act_ld_next();
-  a.ksplit = 1;
-  a.split_stride = 0;
   return launch<OUT_GU_SWIGLU, false>(a, st);
 }
 
@@ -542,27 +489,11 @@ extern "C" int tasu_gemm_nt_bf16_slabs(const void* A, int lda, const void* B, in
       lda % 8 || ldb % 8 || ldc < N)
     return TASU_ERR_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)partials & 15)) return TASU_ERR_ARG;
-  Args a;
-  a.A = (const bf16*)A;
-  a.B = (const bf16*)B;
-  a.C = partials;
-  a.R = nullptr;
-  a.bias = nullptr;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.tiles_m = a.tiles_n = 0;
-  a.act = nullptr;
+  Args a = make_args(A, lda, B, ldb, partials, ldc, nullptr, nullptr, M, N, K);
   a.ksplit = ksplit;
   a.split_stride = (long long)M * ldc;
   return launch<TASU_GEMM_OUT_F32, false>(a, (hipStream_t)stream);
 }
-
-int tasu_gemm_pipe_dispatch(const void* A, int lda, const void* B, int ldb, void* C, int ldc, const void* bias,
-                            const float* resid, int M, int N, int K, int out_mode, int bn, hipStream_t st, int n0, int n1);
 
 // The stream-K work-item lists of tasu_gemm_nt_bf16_streamk for `tiles` output tiles of `pairs` K-tile pairs on `grid`
 // workgroups (host restatement through the kernel's own PpSchedule; no GPU): items[w][i] = {tile, first K-tile, K-tiles, role
@@ -595,7 +526,7 @@ extern "C" int tasu_gemm_nt_bf16_streamk(const void* A, int lda, const void* B, 
   if (!A || !B || !C || !workspace || M <= 0 || N <= 0 || K < 256 || K % 128 || lda % 8 || ldb % 8) return TASU_ERR_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)workspace & 15)) return TASU_ERR_ARG;
   if (out_mode == TASU_GEMM_OUT_F32_RESID_BF16R && !resid) return TASU_ERR_ARG;
-  return tasu_gemm_pp_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, (hipStream_t)stream, 0, 0, workspace,
+  return tasu_gemm_pp_dispatch(tasu_gemm::make_args(A, lda, B, ldb, C, ldc, bias, resid, M, N, K), out_mode, (hipStream_t)stream, workspace,
                                (size_t)workspace_bytes, 1.0);
 }
 
@@ -605,16 +536,17 @@ extern "C" int tasu_gemm_nt_bf16_kernel(const void* A, int lda, const void* B, i
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || K % 64 || lda % 8 || ldb % 8) return TASU_ERR_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return TASU_ERR_ARG;
   if (out_mode == TASU_GEMM_OUT_F32_RESID_BF16R && !resid) return TASU_ERR_ARG;
+  const tasu_gemm::Args a = tasu_gemm::make_args(A, lda, B, ldb, C, ldc, bias, resid, M, N, K);
   switch (kernel) {
     case TASU_GEMM_KERNEL_PP256:
       if (K < 256 || K % 128) return TASU_ERR_ARG;            // an even number (>= 4) of 64-deep K-tiles
-      return tasu_gemm_pp_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, (hipStream_t)stream, 0, 0, nullptr, 0, -2.0);
+      return tasu_gemm_pp_dispatch(a, out_mode, (hipStream_t)stream, nullptr, 0, -2.0);
     case TASU_GEMM_KERNEL_PIPE128:
-      return tasu_gemm_pipe_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, 128, (hipStream_t)stream, 0, 0);
+      return tasu_gemm_pipe_dispatch(a, out_mode, 128, (hipStream_t)stream);
     case TASU_GEMM_KERNEL_PIPE192:
-      return tasu_gemm_pipe_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, 192, (hipStream_t)stream, 0, 0);
+      return tasu_gemm_pipe_dispatch(a, out_mode, 192, (hipStream_t)stream);
     case TASU_GEMM_KERNEL_PIPE96:
-      return tasu_gemm_pipe_dispatch(A, lda, B, ldb, C, ldc, bias, resid, M, N, K, out_mode, 96, (hipStream_t)stream, 0, 0);
+      return tasu_gemm_pipe_dispatch(a, out_mode, 96, (hipStream_t)stream);
     default:
       return TASU_ERR_ARG;
   }

@@ -58,8 +58,8 @@ cases, lda = ldb = K + 8), bias with 256 elements beyond N, R like C: all NaN ou
 slabs) has two guard rows, guard columns up to ldc, `coff` elements in front and 8 behind, and holds a sentinel bit pattern
 everywhere before the launch: `OutBuf.check` requires the sentinel bit for bit outside [M, N] and no NaN inside.
 
-The module also holds the case lists the CPU and the GPU file share (CASES), host restatements of the two policies that have
-no plan entry point (gu_route) and the facts of a stream-K schedule (streamk_facts)."""
+The module also holds the case lists the CPU and the GPU file share (CASES), an independent restatement of the gate|up policy
+(gu_route, which tests/test_gemm_ref64_cpu.py holds to tasu_gemm_gate_up_plan) and the facts of a stream-K schedule (streamk_facts)."""
 import collections
 import ctypes
 import math
@@ -99,8 +99,8 @@ def _modes(via, M, N, K, plan=None, why="", **kw):
                **{k: v for k, v in kw.items() if k != "flip"}) for m in (0, 1, 2)]
 
 
-# ---- every plan of the dispatcher (ops.gemm with the workspace), the smallest shapes that reach it on 256 CUs.  gemm_policy
-# (csrc/gemm.hip): M <= 64 -> the 128-row tiles, pick_bn: 96 wide where ceil(N / 96) / 1.08 > ceil(N / 128), else 128 wide.  Above, the
+# ---- every plan of the dispatcher (ops.gemm with the workspace), the smallest shapes that reach it on 256 CUs.  plan_nt
+# (csrc/gemm_dispatch.h): M <= 64 -> the 128-row tiles, pick_bn: 96 wide where ceil(N / 96) / 1.08 > ceil(N / 128), else 128 wide.  Above, the
 # cost per tile round is 32768 (256 x 128), 28577 (128 x 192), 30720 (256 x 96), 52012 (256 x 256): one-round grids take 128 x 192;
 # 256 x 128 needs ceil(M / 128) ceil(N / 192) > 256 >= ceil(M / 256) ceil(N / 128); 256 x 96 wins only on a tall single column
 # (ceil(M / 256) <= 256 < ceil(M / 128)); whole 256 x 256 tiles need one round of them (52012) under two of the others; the column
@@ -167,7 +167,7 @@ SLAB_CASES = [_c("splitk", "policy", 200, 300, 128, ks=1), _c("splitk", "policy"
 
 
 def gu_route(M, I, K, have_ws=True, cus=CUS):
-    """tasu_gemm_gate_up_swiglu_ws's tile policy (csrc/gemm_pipe.hip), restated: 'pipe' (256 x 128 loader-wave tiles), 'pp' (whole
+    """tasu_gemm_gate_up_swiglu_ws's tile policy (plan_gate_up, csrc/gemm_dispatch.h), restated: 'pipe' (256 x 128 loader-wave tiles), 'pp' (whole
     256 x 256 tiles), 'pp+pipe' (whole rounds of 256 x 256 + the remaining columns on 256 x 128 in a second launch) or 'pp-sk' (256 x 256
     tiles cut along K).  In units of a 256 x 256 round: c128 = rounds(tm ceil(I / 64)) / 2, c256_whole = rounds(tm tn) / 1.26,
     c256_sk = tm tn / cus / 1.26 + 1e8 / K / 52012 where sk_plan(tm tn, K / 128, cus, max_rem = 0) > 0."""
@@ -189,6 +189,9 @@ def gu_route(M, I, K, have_ws=True, cus=CUS):
     if full >= 1 and 0 < tn_main < tn and full / 1.26 + rounds(tm * (tn - tn_main) * 2) * 0.5 + 0.05 < whole:
         return "pp+pipe"
     return "pp"
+
+
+GU_PLAN = {"pipe": 1, "pp": 2, "pp+pipe": 3, "pp-sk": 4}       # TASU_GEMM_GU_PLAN_* (include/tasu_hip.h): tasu_gemm_gate_up_plan
 
 
 # ---- gate|up + SwiGLU.  pp: rounds(tm tn) / 1.26 < rounds(tm ceil(I / 64)) / 2 first holds at one round against two: two tile rows,

@@ -46,6 +46,11 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.tasu_gemm_stream_qkv_rope_rstd(None, 1536, None, 1536, None, None, 64, 12, 2, 1536, None, None, None, None, None, 328, None, 96,
                                               1e-6, 1, 1, None) == 1
     assert lib.tasu_stream_finish_norm(None, 13, None, None, 64, 3584, None, None, 1e-6, 1, None) == 1
+    # the gate|up plan: what tasu_gemm_gate_up_swiglu_ws refuses (I % 4, K % 64; non-positive sizes)
+    assert lib.tasu_gemm_gate_up_plan(4096, 8960, 1536, 1) > 0
+    assert lib.tasu_gemm_gate_up_plan(4096, 8962, 1536, 1) == -1 and lib.tasu_gemm_gate_up_plan(4096, 8960, 1504, 1) == -1
+    assert lib.tasu_gemm_gate_up_plan(0, 8960, 1536, 1) == -1 and lib.tasu_gemm_gate_up_plan(4096, 0, 1536, 0) == -1
+    assert lib.tasu_gemm_gate_up_plan(4096, 8960, 0, 0) == -1
 
 
 def test_stream_k_ranges_equal_and_ragged():
@@ -130,42 +135,61 @@ def test_streamk_schedule_covers_every_tile_once_and_cannot_deadlock(tiles, pair
         assert work.max() - work.min() <= 2 * pairs + 16 if tiles > grid else work.max() - work.min() <= 16   # balanced up to the snapping
 
 
+PP, PP_P128, PP_P192, SK, P128, P192, P96, SPLITK, TILES = range(1, 10)
+BF, F32, RES = 0, 1, 2
+M = 4096
+STEP_PLANS = [
+    ((M, 2048, 1536, BF), P128),            # q|k|v (the step itself runs tasu_gemm_qkv_rope: the same 256 x 128 tiles)
+    ((M, 1536, 1536, RES), P192),           # o: one round of 128 x 192
+    ((M, 1536, 1536, BF), P192),            # d_o
+    ((M, 1536, 2048, BF), P192),            # d_qkv
+    ((M, 1536, 8960, RES), P192),           # down: the cut loses at K = 8960 (108 against 100 us)
+    ((M, 8960, 1536, BF), PP_P192),         # d_down: two whole rounds + column tail
+    ((M, 17920, 1536, BF), PP_P192),        # gate|up as a plain GEMM: four whole rounds + column tail
+    ((M, 1536, 17920, BF), SK),             # d_gate_up: 96 tiles on 256 CUs, stream-K
+    ((2048, 151936, 1536, BF), PP),         # lm_head on the labelled rows
+    ((1664, 2048, 25088, BF), SK),          # projector
+    ((M, 3584, 18944, RES), PP),            # 7B down: 224 tiles, whole (the cut loses above 3/4 of a round)
+    ((M, 3584, 37888, BF), PP),             # 7B d_gate_up
+    ((2048, 1536, 17920, BF), SK),          # batch 8: 48 tiles
+    ((2048, 1536, 8960, RES), SK),
+    ((3072, 1536, 17920, BF), P192),        # batch 12: 72 tiles, K offsets not aligned within an XCD
+    ((1024, 1536, 17920, BF), SK),          # 24 tiles: up to a quarter round the offsets do not matter
+    ((1024, 1536, 8960, BF), P192),         # ... but 6.5 K-tile pairs per CU are too few
+    ((512, 1536, 17920, BF), SPLITK),       # nothing else fills the chip
+    ((128, 1536, 8960, BF), P192),
+    ((64, 1536, 1536, BF), TILES),
+]
+
+
 def test_gemm_policy_on_the_training_step_shapes():
     """tasu_gemm_plan: the dispatcher's choice (no launch, no GPU) for the GEMM shapes of the benchmark step and its neighbours --
     the measured winners of profiles/r03_gemm_lab.txt / r03_gemm_streamk.txt.  A policy edit that moves one of them shows up here
     (round 3: the stream-K option once shadowed whole 256 x 256 tiles and cost the 7B and audio-SFT steps 6-8 %)."""
     from ps_slm_amd import _lib
     lib = _lib.load()
-    PP, PP_P128, PP_P192, SK, P128, P192, P96, SPLITK, TILES = range(1, 10)
-    BF, F32, RES = 0, 1, 2
-    M = 4096
-    want = [
-        ((M, 2048, 1536, BF), P128),            # q|k|v (the step itself runs tasu_gemm_qkv_rope: the same 256 x 128 tiles)
-        ((M, 1536, 1536, RES), P192),           # o: one round of 128 x 192
-        ((M, 1536, 1536, BF), P192),            # d_o
-        ((M, 1536, 2048, BF), P192),            # d_qkv
-        ((M, 1536, 8960, RES), P192),           # down: the cut loses at K = 8960 (108 against 100 us)
-        ((M, 8960, 1536, BF), PP_P192),         # d_down: two whole rounds + column tail
-        ((M, 17920, 1536, BF), PP_P192),        # gate|up as a plain GEMM: four whole rounds + column tail
-        ((M, 1536, 17920, BF), SK),             # d_gate_up: 96 tiles on 256 CUs, stream-K
-        ((2048, 151936, 1536, BF), PP),         # lm_head on the labelled rows
-        ((1664, 2048, 25088, BF), SK),          # projector
-        ((M, 3584, 18944, RES), PP),            # 7B down: 224 tiles, whole (the cut loses above 3/4 of a round)
-        ((M, 3584, 37888, BF), PP),             # 7B d_gate_up
-        ((2048, 1536, 17920, BF), SK),          # batch 8: 48 tiles
-        ((2048, 1536, 8960, RES), SK),
-        ((3072, 1536, 17920, BF), P192),        # batch 12: 72 tiles, K offsets not aligned within an XCD
-        ((1024, 1536, 17920, BF), SK),          # 24 tiles: up to a quarter round the offsets do not matter
-        ((1024, 1536, 8960, BF), P192),         # ... but 6.5 K-tile pairs per CU are too few
-        ((512, 1536, 17920, BF), SPLITK),       # nothing else fills the chip
-        ((128, 1536, 8960, BF), P192),
-        ((64, 1536, 1536, BF), TILES),
-    ]
-    for (m, n, k, mode), plan in want:
+    for (m, n, k, mode), plan in STEP_PLANS:
         assert lib.tasu_gemm_plan(m, n, k, mode, 1) == plan, (m, n, k, mode, lib.tasu_gemm_plan(m, n, k, mode, 1), plan)
     # without the workspace the stream-K schedule is not available
     assert lib.tasu_gemm_plan(M, 1536, 17920, BF, 0) == P192
     assert lib.tasu_gemm_plan(M, 1536, 17920, 5, 1) == -1 and lib.tasu_gemm_plan(M, 1536, 100, BF, 1) == -1
+
+
+def test_gemm_plans_equal_the_stored_grid():
+    """tests/golden/gemm_plan_grid.txt: tasu_gemm_plan over 13 x 14 x 10 shapes (every M, N, K at which the policy changes its mind on
+    the models' geometries, and their neighbours), the three output modes, with and without the workspace, plus the shapes of
+    tests/gemm_ref64.py's plan cases and of STEP_PLANS above, on 256 compute units (plan_nt, csrc/gemm_dispatch.h).  An edit of the
+    policy shows its plan diff here and refreshes the file on purpose; an edit that is not meant to move a plan leaves it alone."""
+    from ps_slm_amd import _lib
+    lib = _lib.load()
+    rows = [tuple(int(v) for v in line.split()) for line in open(os.path.join(ROOT, "tests", "golden", "gemm_plan_grid.txt"))
+            if not line.startswith("#")]
+    assert len(rows) > 10000 and {r[5] for r in rows} == set(range(1, 10))          # every TASU_GEMM_PLAN_* value
+    stored = {r[:5]: r[5] for r in rows}
+    for (m, n, k, mode), plan in STEP_PLANS:
+        assert stored[(m, n, k, mode, 1)] == plan
+    moved = [(r, lib.tasu_gemm_plan(*r[:5])) for r in rows if lib.tasu_gemm_plan(*r[:5]) != r[5]]
+    assert not moved, f"{len(moved)} plans moved (M, N, K, mode, workspace, stored plan), now: {moved[:20]}"
 
 
 def test_rccl_binding_picks_the_mapped_copy_and_refuses_a_second_one():

@@ -6,8 +6,9 @@ tests/test_gpu_gemm_f64.py holds the HIP kernels to:
   the double: N(0, 1) linear outputs 0.991 (one bf16 rounding alone reaches u |c| just above a power of two), SwiGLU 0.961,
   bias + RoPE 0.996, dswiglu 0.996 on exact accumulations;
 * the case lists reach what their comments name: every TASU_GEMM_PLAN_* value through tasu_gemm_plan (host code), every route of
-  the gate|up policy (gemm_ref64.gu_route, a hand restatement: that policy has no plan entry point, so an edit of it is NOT
-  caught here), and the stream-K conditions through tasu_streamk_schedule -- a later edit of the dispatcher's policy or of the
+  the gate|up policy through tasu_gemm_gate_up_plan (the planner the entry point launches from; gemm_ref64.gu_route, a hand
+  restatement of the policy, is held to it over a grid of 1008 shapes, so an edit of the policy that moves a route IS caught
+  here), and the stream-K conditions through tasu_streamk_schedule -- a later edit of the dispatcher's policy or of the
   schedule cannot quietly empty a path of its cases;
 * the checks have teeth.  These are mutants of the RESTATED pipeline (fp32 torch, below), each with its score under the
   tensor-wide metric of tests/test_gpu_ops.py (max|a-b| / max|b| < 1e-2, 2e-2 for the fused epilogues, 2e-5 sqrt(K) in fp32 mode)
@@ -115,7 +116,7 @@ def test_case_list_reaches_every_plan(lib):
         assert got == c.plan, f"{G.case_id(c)}: the dispatcher plans {G.PLAN_NAMES.get(got, got)}, the list names {G.PLAN_NAMES[c.plan]}"
         seen.add(got)
     assert seen == set(G.PLAN_NAMES), f"no case for {[G.PLAN_NAMES[p] for p in set(G.PLAN_NAMES) - seen]}"
-    # both pick_bn outcomes below 65 rows (csrc/gemm.hip, restated): 96 wide where ceil(N / 96) / 1.08 > ceil(N / 128)
+    # both pick_bn outcomes below 65 rows (csrc/gemm_dispatch.h, restated): 96 wide where ceil(N / 96) / 1.08 > ceil(N / 128)
     bn = {96 if -(-c.N // 96) / 1.08 > -(-c.N // 128) else 128 for c in G.PLAN_CASES if c.plan == G.TILES}
     assert bn == {96, 128}
     assert any(c.M == 1 and c.N % 16 for c in G.PLAN_CASES if c.plan == G.TILES)
@@ -130,9 +131,10 @@ def test_case_list_reaches_every_plan(lib):
             assert -(-c.M // 256) * -(-c.N // 256) > 256
 
 
-def test_gate_up_cases_reach_every_route():
+def test_gate_up_cases_reach_every_route(lib):
     for c in G.SWIGLU_CASES:
         assert G.gu_route(c.M, c.N, c.K) == c.via, (G.case_id(c), G.gu_route(c.M, c.N, c.K))
+        assert lib.tasu_gemm_gate_up_plan(c.M, c.N, c.K, 1) == G.GU_PLAN[c.via], G.case_id(c)
     assert {c.via for c in G.SWIGLU_CASES} == {"pipe", "pp", "pp+pipe", "pp-sk"}
     assert any(c.N % 128 for c in G.SWIGLU_CASES) and any(c.N % 8 == 4 for c in G.SWIGLU_CASES)
     assert any(c.coff for c in G.SWIGLU_CASES) and any(c.pad for c in G.SWIGLU_CASES)
@@ -140,6 +142,17 @@ def test_gate_up_cases_reach_every_route():
     # and its stream-K case
     assert G.gu_route(4096, 8960, 1536) == "pp+pipe" and G.gu_route(2048, 1536, 16384) == "pp-sk"
     assert G.gu_route(2048, 1536, 16384, have_ws=False) != "pp-sk"
+    # the library's planner against the restatement
+    seen = {}
+    for M in (1, 64, 65, 256, 300, 512, 2048, 4096, 8192):
+        for I in (128, 200, 1024, 1536, 8320, 8960, 18944, 32896):
+            for K in (64, 128, 256, 1536, 3584, 16384, 17920):
+                for ws in (0, 1):
+                    want = G.gu_route(M, I, K, have_ws=bool(ws))
+                    assert lib.tasu_gemm_gate_up_plan(M, I, K, ws) == G.GU_PLAN[want], (M, I, K, ws, want)
+                    seen[want] = seen.get(want, 0) + 1
+    print(f"GU ROUTES over the grid: {seen}")
+    assert set(seen) == set(G.GU_PLAN)                           # (pipe 752, pp 118, pp+pipe 120, pp-sk 18 of the 1008)
 
 
 def test_streamk_cases_meet_the_schedule_conditions(lib):

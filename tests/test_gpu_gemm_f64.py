@@ -15,9 +15,11 @@ The exact profile's BITS for every linear output (all fp32-mode results and ever
 and dswiglu on exact accumulations; on the N(0, 1) profile (K <= 512) E = u |c| + the rigorous fp32 allowance per element and
 rms(err / (u |c|)) at most 1.5 x the torch double's.  Operand guards are NaN; every output buffer holds a sentinel pattern before
 the launch and must keep it, bit for bit, outside [M, N].  Cases that go through the workspace run twice (equal bits) and leave
-its flag and counter words zero.
+its flag and counter words zero.  The launch is the plan: every dispatched case launches as many GEMM kernels
+(tasu_gemm_launch_count) as the plan the library names for it (tasu_gemm_plan, tasu_gemm_gate_up_plan) stands for -- two for a
+column split, else one -- and no epilogue option (ReLU, act's leading dimension) outlives the call it was given to.
 
-Measured on an MI355X (the F64RATIO / F64EXACT / F64N01 lines this file prints): 118 tests, 12 s.  Every exact-bits check
+Measured on an MI355X (the F64RATIO / F64EXACT / F64N01 lines this file prints): 118 tests, 12 s (the four option tests came later).  Every exact-bits check
 holds on every route.  Largest kernel rms / double rms over the 73 statistics taken: 1.000 (every family and output).  Largest
 |err| / E per family, equal to the double's to three digits: exact accumulations -- SwiGLU 0.961, bias + RoPE 0.996, dswiglu 0.996;
 N(0, 1) -- gemm 0.991, bias + ReLU 0.983, gate|up 0.985, q|k|v 0.989, dswiglu (dact) 0.985, split-K 0.981, slabs 0.967.  No kernel
@@ -59,6 +61,18 @@ def report(family, name, kernel, double, case):
                                             f"(at most {G.RMS_RATIO} x: a systematic error, not rounding)")
 
 
+def planned_launches(hip, c):
+    """GEMM kernel launches behind the case's call, from the plan the LIBRARY names for it (which must be the list's); None where
+    the case is not dispatched"""
+    if c.op == "swiglu":
+        assert hip.lib.tasu_gemm_gate_up_plan(c.M, c.N, c.K, 1) == G.GU_PLAN[c.via], G.case_id(c)
+        return 2 if c.via == "pp+pipe" else 1
+    if c.plan is None:
+        return None
+    assert hip.lib.tasu_gemm_plan(c.M, c.N, c.K, c.mode if c.op == "plain" else 0, 1) == c.plan, G.case_id(c)
+    return 2 if c.plan in (G.PP_P128, G.PP_P192) else 1
+
+
 def run_case(hip, c, d):
     """One case through HipOps: name -> CPU result [M, N] (the names of gemm_ref64.reference).  Operands carry their NaN guards,
     every output starts as the sentinel pattern; OutBuf.check holds the guard rows, columns and margins to it."""
@@ -73,6 +87,7 @@ def run_case(hip, c, d):
         outs[name] = (b, flat)
         return b.view(flat)
 
+    launches, before = planned_launches(hip, c), hip.lib.tasu_gemm_launch_count()
     if c.op in ("plain", "relu"):
         cv = buf("c", M, N, N + c.pad, BF if c.mode == 0 else F32, c.coff)
         R = None if d["resid"] is None else d["resid_buf"].view(d["resid"].cuda())
@@ -100,6 +115,9 @@ def run_case(hip, c, d):
         else:
             hip.gemm_slabs(a, w, ws, M, N, K, c.ks)
             hip.sum_slabs(ws, c.ks, cv, M * N)
+    if launches is not None:
+        got = hip.lib.tasu_gemm_launch_count() - before
+        assert got == launches, f"{what}: {got} GEMM launches, the plan stands for {launches}"
     torch.cuda.synchronize()
     res = {name: b.check(flat, f"{what} {name}") for name, (b, flat) in outs.items()}
     if c.op == "qkv":
@@ -142,6 +160,60 @@ def test_gemm_against_float64(hip, fake, case):
         assert bool(torch.isfinite(got).all()), f"{what}: {name} is not finite on the N(0, 1) profile"
         if got.numel() >= 4096:                                  # (fewer elements: the statistic is noise)
             report(family, name, G.rms_ulp(got, want, mag), want_rms[name], what)
+
+
+@pytest.mark.parametrize("relu_first", [True, False], ids=["relu-then-plain", "plain-then-relu"])
+def test_relu_does_not_outlive_its_call(hip, relu_first):
+    """bias + ReLU on a fused plan, and the plain GEMM with bias on the same operands, in either order: each gives its own exact
+    bits -- the plain result keeps its negative values"""
+    cr = [c for c in G.RELU_CASES if (c.M, c.N, c.K) == (300, 520, 256)][0]
+    cp = cr._replace(op="plain")
+    assert hip.lib.tasu_gemm_plan(cr.M, cr.N, cr.K, 0, 1) not in (G.TILES, G.SPLITK), "not a fused plan"
+    d = G.make_inputs(cp, "exact")
+    want = {True: G.reference(cr, d).exact["c"], False: G.reference(cp, d).exact["c"]}
+    assert bool((want[False] < 0).any()) and not torch.equal(want[True], want[False])
+    a, w, bias = d["a"].cuda(), d["w"].cuda(), d["bias"].cuda()
+    bufs = {}
+    for relu in (relu_first, not relu_first):
+        b = G.OutBuf(cr.M, cr.N, cr.N + cr.pad, BF)
+        flat = b.flat.cuda()
+        (hip.gemm_bias_relu if relu else hip.gemm)(a, w, b.view(flat), cr.M, cr.N, cr.K, bias=bias)
+        bufs[relu] = (b, flat)
+    torch.cuda.synchronize()
+    for relu, (b, flat) in bufs.items():
+        what = f"{'bias + ReLU' if relu else 'plain'} ({'first' if relu == relu_first else 'second'} call)"
+        G.assert_bits(b.check(flat, what), want[relu], what, cr.K)
+    assert bool((bufs[False][0].check(bufs[False][1], "plain") < 0).any())
+
+
+@pytest.mark.parametrize("ld_first", [True, False], ids=["ld-then-dense", "dense-then-ld"])
+def test_act_leading_dimension_does_not_outlive_its_call(hip, ld_first):
+    """gate|up + SwiGLU with act inside a wider buffer (the _ld form), and the dense form at the same shape, in either order.  The
+    dense act sits at the head of a buffer as large as the padded one, so that a leading dimension carried over from the other call
+    would land inside it: everything behind the dense [M, I] keeps the sentinel."""
+    cl = [c for c in G.SWIGLU_CASES if c.pad == 64][0]
+    cd = cl._replace(pad=0)
+    M, I, K, ld = cl.M, cl.N, cl.K, cl.N + cl.pad
+    d = G.make_inputs(cd, "exact")
+    ref = G.reference(cd, d)
+    a, w = d["a"].cuda(), d["w"].cuda()
+    res = {}
+    for padded in (ld_first, not ld_first):
+        gu, act = G.OutBuf(M, 2 * I, 2 * I, BF), G.OutBuf(M, I, ld, BF)
+        gflat, aflat = gu.flat.cuda(), act.flat.cuda()
+        hip.gemm_gate_up_swiglu(a, w, gu.view(gflat), act.view(aflat) if padded else aflat[:M * I].view(M, I), M, I, K)
+        res[padded] = (gu, gflat, act, aflat)
+    torch.cuda.synchronize()
+    for padded, (gu, gflat, act, aflat) in res.items():
+        what = f"{'_ld' if padded else 'dense'} form ({'first' if padded == ld_first else 'second'} call)"
+        if padded:
+            got = act.check(aflat, f"{what} act")
+        else:
+            flat = aflat.cpu()
+            assert torch.equal(G._bits(flat[M * I:]), G._bits(act.flat[M * I:])), f"{what}: act was written behind its dense [M, I]"
+            got = flat[:M * I].view(M, I)
+            assert not bool(torch.isnan(got).any())
+        G.check_case(cd, d, ref, dict(gu=gu.check(gflat, f"{what} gu"), act=got), what)
 
 
 def test_gemm_entry_points_refuse_what_they_do_not_serve(hip):

@@ -592,7 +592,7 @@ int tasu_beam_update(const float* vals, const int32_t* idx, float* run_scores, f
                      int32_t* next_ids, int32_t* next_src, int32_t* next_pos, int32_t* next_slot, int32_t* next_lens,
                      int32_t* banned, int B, int n_beams, int max_new, int eos, int min_length, int S, int first,
                      void* stream);
-/* generate(repetition_penalty = p != 1): HF RepetitionPenaltyLogitsProcessor on the device decode loop (csrc/topk_hist.hip).
+/* generate(repetition_penalty = p != 1): HF RepetitionPenaltyLogitsProcessor on the device decode loop (csrc/topk.hip, csrc/beam.hip).
  * tasu_beam_hist_update, after tasu_beam_update: hist [B * n_beams, max_new] (row stride max_new) becomes, per row m, the history
  * of its parent row next_src[m] plus its new token next_ids[m], in place (one workgroup per utterance; parents are rows of the same
  * utterance), and hist_len[m] = ctl[0]; a no-op once ctl[1] (done) is set.  max_new <= 2048, n_beams <= 16. */

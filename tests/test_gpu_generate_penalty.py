@@ -1,4 +1,4 @@
-"""generate(repetition_penalty = p) on the GPU (csrc/topk_hist.hip): the history top-k kernels against a float64 restatement, the
+"""generate(repetition_penalty = p) on the GPU (csrc/topk.hip, csrc/beam.hip): the history top-k kernels against a float64 restatement, the
 history kernel against numpy (eager and under one captured-and-replayed graph), and the decode paths end to end against the REAL
 reference's tokens (tests/golden/mid_generate_penalty.npz)."""
 import types

@@ -1,5 +1,5 @@
 """generate(num_beams = 5 .. 16) on the GPU: the four top-k entry points at k up to 32 against a float64 restatement, the wide beam
-update (csrc/decode.hip::beam_update_wide_kernel) against BeamState and the CPU double after every step of scripted candidate
+update (csrc/beam.hip::beam_update_wide_kernel) against BeamState and the CPU double after every step of scripted candidate
 streams, the wide history kernel against numpy, and the decode paths end to end against the REAL reference's tokens
 (tests/golden/mid_generate_wide.npz)."""
 import types
@@ -133,6 +133,21 @@ def test_plain_topk_kernels_vs_float64(ops, dtype, V, M):
         check_topk(call, lg, V, banned, want_v, want_i, k, BAR[dtype], f"{dtype} M={M} V={V}")
 
 
+def test_plain_topk_bf16_part_longer_than_the_register_window(ops):
+    """tasu_logprob_topk at V = 196,672: 16 parts of 1537 chunks of 8 columns, one more than the 256 x 6 chunks the part scan holds
+    in registers, so the first 15 parts take the per-thread lists (csrc/topk.hip::topk_part_lists) for the whole part, the loop past
+    the register window included; the last part holds the remaining 1529 chunks and runs the threshold form.  M = 5: every row kind of ``crafted``, the constant row and the row with fewer than k finite columns among them."""
+    M, V = 5, 196672
+    lg, hist, hl, banned = crafted(M, V, torch.bfloat16, seed=31)
+    assert lg.shape[1] == V and -(-(-(-V // 8)) // 16) == 256 * 6 + 1
+    want_v, want_i = reference(lg, V, hist, hl, banned, None, -1)
+    for k in (4, 10, 32):
+        def call(k, val, idx, ws):
+            ops.topk_ws[:ws.numel()] = ws
+            ops.logprob_topk(lg, M, V, k, banned, 1, val, idx)
+        check_topk(call, lg, V, banned, want_v, want_i, k, BAR[torch.bfloat16], f"bf16 long parts M={M} V={V}")
+
+
 @pytest.mark.parametrize("M", [1, 3, 70])
 @pytest.mark.parametrize("V", [1000, 151936])
 @pytest.mark.parametrize("mode", [0, 1])
@@ -218,11 +233,11 @@ def test_beam_update_refuses_17_beams(ops):
         ops.beam_update(v, i, bs, False)
 
 
-# ------------------------------------------------------------------------------------------ 3. the history kernel, wide
-@pytest.mark.parametrize("nb", [6, 16])
+# ------------------------------------------------------------------------------------------ 3. the history kernel, every width
+@pytest.mark.parametrize("nb", [1, 5, 6, 16])
 def test_wide_history_kernel_follows_the_parents(ops, nb):
-    """More than 5 beams stage the rows 512 positions at a time: histories of 1, 2, 512, 513, 514, 1025 and 1300 positions (one, two and
-    three passes), two rows of an utterance sharing a parent; columns past the history and a call after done stay untouched."""
+    """The rows are staged 512 positions at a time at every width: histories of 1, 2, 512, 513, 514, 1025 and 1300 positions (one, two and
+    three passes), two rows of an utterance sharing a parent (nb > 1); columns past the history and a call after done stay untouched."""
     B, max_new = 3, 1300
     M = B * nb
     rng = np.random.default_rng(5)
@@ -233,7 +248,8 @@ def test_wide_history_kernel_follows_the_parents(ops, nb):
     bs.hist.copy_(torch.from_numpy(ref))
     for n in (1, 2, 512, 513, 514, 1025, 1300):
         par = rng.integers(0, nb, (B, nb))
-        par[:, 1] = par[:, 0]
+        if nb > 1:
+            par[:, 1] = par[:, 0]
         src = (np.arange(B)[:, None] * nb + par).reshape(-1)
         ids = rng.integers(0, 1000, M).astype(np.int32)
         new = ref.copy()

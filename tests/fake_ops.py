@@ -464,8 +464,9 @@ class FakeOps:
     # ---------------------------------------------------------------- optimizer
     def adamw(self, p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale):
         lr = float(torch.tensor(lr, dtype=torch.float32))        # the kernel takes lr as a C float
-        gr = g * grad_scale
-        m.mul_(beta1).add_(gr, alpha=1 - beta1)
+        beta1, beta2 = float(np.float32(beta1)), float(np.float32(beta2))     # ... and the betas: `1.f - beta` on the device and the
+        gr = g * grad_scale                                                    # host's bias corrections are formed from THOSE values
+        m.mul_(beta1).add_(gr, alpha=1 - beta1)                                # (1 - 0.999f = 0.00099998713, not 0.001; exact in fp32)
         v.mul_(beta2).addcmul_(gr, gr, value=1 - beta2)
         bc1 = 1 - beta1 ** step
         bc2 = 1 - beta2 ** step

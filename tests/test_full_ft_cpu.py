@@ -149,7 +149,13 @@ def test_full_ft_names_layout_and_ranges(tied):
 @pytest.mark.parametrize("tied", [True, False])
 def test_full_ft_engine_step_equals_torch_adamw_and_autograd_route(tied):
     """One TasuEngine step = torch.optim.AdamW over model.parameters() on the same gradients (loss.backward() through _HipStep), to
-    the existing engine test's tolerance; afterwards the kernels' copies follow the masters."""
+    the existing engine test's tolerance; afterwards the kernels' copies follow the masters.  The key biases are the exception in
+    the second step: their gradient is pure cancellation (a softmax does not see a constant added to every key's score; median
+    5e-6 here), so masters that differ in the last place after the first step -- two AdamW formulations -- give the two sides
+    different noise there (single elements moved by 1 %), and Adam normalises noise to full-size steps.  All that can be said of
+    such an element is that each side moved it by at most one step: with two gradients in the moments |m^| / sqrt(v^) <=
+    sqrt(w1^2 / a1 + w2^2 / a2) = 1.0014 (Cauchy-Schwarz; w = (b1 c1, c1) / bc1, a = (b2 c2, c2) / bc2), so the two differ by at
+    most 2.003 lr.  Every other parameter keeps the two-step comparison at the old tolerance."""
     model, _ = make_ft(tied=tied, seed=77)
     twin, eng = make_ft(tied=tied, seed=77)
     geo = model.core.geo
@@ -173,7 +179,8 @@ def test_full_ft_engine_step_equals_torch_adamw_and_autograd_route(tied):
         opt.step()
         sd, sd_e = model.state_dict(), twin.state_dict()
         for k in sd:
-            assert torch.allclose(sd[k], sd_e[k], rtol=2e-5, atol=2e-7), (step, k)
+            noise = step > 0 and k.endswith("self_attn.k_proj.bias")
+            assert torch.allclose(sd[k], sd_e[k], rtol=2e-5, atol=2.003 * lr if noise else 2e-7), (step, k)
     core, llm = twin.core, twin.core.llm
     w = llm.layers[0]
     V = geo.llm_vocab

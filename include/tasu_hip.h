@@ -252,7 +252,8 @@ int tasu_gemm_skinny_swiglu(const void* A, int lda, const void* Wgu, int ldw, vo
  * cols<=C outside [R,C) of `out` up to (Cpad, Rpad) are written as zero so K-padding stays exact.       */
 int tasu_transpose_bf16(const void* in, int ld_in, void* out, int ld_out, int R, int C, int Rpad, int Cpad,
                         void* stream);
-/* fp32 -> bf16 cast (same layout) and fp32 -> bf16 transposed copy; n / R x C as above.                */
+/* fp32 -> bf16 cast (same layout) and fp32 -> bf16 transposed copy; n / R x C as above.  The cast reads 16-byte and writes
+ * 8-byte vectors: `in` 16-byte, `out` 8-byte aligned, else TASU_ERR_ARG.                                   */
 int tasu_cast_f32_bf16(const void* in, void* out, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------- RMSNorm
@@ -290,7 +291,9 @@ int tasu_rope_table(const int32_t* pos, float* cos_tab, float* sin_tab, int M, i
  * 113-135, fp32 math, bf16 result):
  *   qkv    [M, (H+2G)*128] bf16 : q heads | k heads | v heads
  *   qt     [B, H, 128, S], kt [B, G, 128, S], vt [B, G, 128, S]: OPTIONAL transposed copies (NULL = not written; the
- *   attention kernels no longer read them: since round 2 they transpose in LDS with ds_read_b64_tr_b16)       */
+ *   attention kernels no longer read them: since round 2 they transpose in LDS with ds_read_b64_tr_b16)
+ *   qkv, qt, kt, vt (and, for tasu_rope_bwd, dqkv, both partial buffers and both tables) are accessed in 16-byte vectors:
+ *   a pointer that is not 16-byte aligned is refused with TASU_ERR_ARG.                                        */
 int tasu_rope_fwd(void* qkv, const float* cos_tab, const float* sin_tab, void* qt, void* kt, void* vt,
                   int B, int S, int H, int G, void* stream);
 /* Autograd of the above on dqkv [M,(H+2G)*128]: the q block (dQ in rotated space, written by tasu_attn_bwd_dq)
@@ -372,7 +375,8 @@ int tasu_attn_bwd_fused(const void* qkv, const uint8_t* key_mask, const void* do
 
 /* -------------------------------------------------------------------------------------------- SwiGLU
  * act = bf16(bf16(silu(gate)) * up) on the fused [M, 2I] gate|up activation (modeling_qwen2.py:46-48),
- * and its backward dgu = [dact*up*silu'(gate) | dact*silu(gate)].                                        */
+ * and its backward dgu = [dact*up*silu'(gate) | dact*silu(gate)].  Every pointer of the SwiGLU, SiLU and ReLU entry points
+ * is accessed in 16-byte vectors and must be 16-byte aligned (TASU_ERR_ARG otherwise).                    */
 int tasu_swiglu_fwd(const void* gu, void* act, int M, int I, void* stream);
 int tasu_swiglu_bwd(const void* dact, const void* gu, void* dgu, int M, int I, void* stream);
 /* Plain SiLU (projector.py:142) fwd/bwd, bf16, and ReLU (SenseVoice.py:63) fwd.                         */

@@ -193,39 +193,46 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16* __restr
 
 extern "C" int tasu_swiglu_fwd(const void* gu, void* act, int M, int I, void* stream) {
   if (!gu || !act || M <= 0 || I <= 0 || I % 8) return TASU_ERR_ARG;
+  if (((uintptr_t)gu | (uintptr_t)act) & 15) return TASU_ERR_ARG;                     // 16-byte vectors
   TASU_LAUNCH(swiglu_fwd_kernel, dim3(grid_for((int64_t)M * I / 8)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)gu, (bf16*)act, M, I);
   return TASU_OK;
 }
 extern "C" int tasu_swiglu_bwd(const void* dact, const void* gu, void* dgu, int M, int I, void* stream) {
   if (!dact || !gu || !dgu || M <= 0 || I <= 0 || I % 8) return TASU_ERR_ARG;
+  if (((uintptr_t)dact | (uintptr_t)gu | (uintptr_t)dgu) & 15) return TASU_ERR_ARG;
   TASU_LAUNCH(swiglu_bwd_kernel, dim3(grid_for((int64_t)M * I / 8)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)dact, (const bf16*)gu, (bf16*)dgu, M, I);
   return TASU_OK;
 }
 extern "C" int tasu_silu_fwd(const void* x, void* y, int64_t n, void* stream) {
   if (!x || !y || n <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)y) & 15) return TASU_ERR_ARG;
   TASU_LAUNCH(unary_kernel<0>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, n);
   return TASU_OK;
 }
 extern "C" int tasu_relu_fwd(const void* x, void* y, int64_t n, void* stream) {
   if (!x || !y || n <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)y) & 15) return TASU_ERR_ARG;
   TASU_LAUNCH(unary_kernel<1>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, n);
   return TASU_OK;
 }
 extern "C" int tasu_silu_bwd(const void* dy, const void* x, void* dx, int64_t n, void* stream) {
   if (!dy || !x || !dx || n <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx) & 15) return TASU_ERR_ARG;
   TASU_LAUNCH(silu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy,
                      (const bf16*)x, (bf16*)dx, n);
   return TASU_OK;
 }
 extern "C" int tasu_relu_bwd(const void* dy, const void* x, void* dx, int64_t n, void* stream) {
   if (!dy || !x || !dx || n <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx) & 15) return TASU_ERR_ARG;
   TASU_LAUNCH(relu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)x, (bf16*)dx, n);
   return TASU_OK;
 }
 extern "C" int tasu_cast_f32_bf16(const void* in, void* out, int64_t n, void* stream) {
   if (!in || !out || n <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)in & 15) || ((uintptr_t)out & 7)) return TASU_ERR_ARG;               // f32x4 loads, bf16x4 stores
   TASU_LAUNCH(cast_f32_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)in,
                      (bf16*)out, n);
   return TASU_OK;

@@ -181,6 +181,7 @@ extern "C" int tasu_rope_table(const int32_t* pos, float* cos_tab, float* sin_ta
 extern "C" int tasu_rope_fwd(void* qkv, const float* cos_tab, const float* sin_tab, void* qt, void* kt, void* vt, int B,
                              int S, int H, int G, void* stream) {
   if (!qkv || !cos_tab || !sin_tab || B <= 0 || S <= 0 || H <= 0 || G <= 0) return TASU_ERR_ARG;
+  if (((uintptr_t)qkv | (uintptr_t)qt | (uintptr_t)kt | (uintptr_t)vt) & 15) return TASU_ERR_ARG;   // 16-byte vectors (the tables: scalars)
   // without transposed copies only the q and k heads have work (the v heads are not rotated)
   dim3 grid((S + 63) / 64, (qt || kt || vt) ? H + 2 * G : H + G, B);
   TASU_LAUNCH(rope_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (bf16*)qkv, cos_tab, sin_tab, (bf16*)qt,
@@ -192,6 +193,7 @@ extern "C" int tasu_rope_bwd(void* dqkv, const float* dk_part, const float* dv_p
                              const float* sin_tab, int B, int S, int H, int G, void* stream) {
   if (!dqkv || !dk_part || !dv_part || !cos_tab || !sin_tab || B <= 0 || S <= 0 || H <= 0 || G <= 0 || H % G)
     return TASU_ERR_ARG;
+  if (((uintptr_t)dqkv | (uintptr_t)dk_part | (uintptr_t)dv_part | (uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15) return TASU_ERR_ARG;
   const int upt = (H + 2 * G) * 8;
   const int tpb = upt <= 128 ? 256 / upt : 1, M = B * S;
   TASU_LAUNCH(rope_bwd_kernel, dim3((M + tpb - 1) / tpb), dim3(256), 0, (hipStream_t)stream, (bf16*)dqkv, dk_part, dv_part,

@@ -490,12 +490,12 @@ class FakeOps:
 
     def fsmn_fwd(self, v, ldv, w, lens, out, B, T, D, ksize, accumulate):
         vv = v.reshape(B, T, -1)[..., :D].float()
-        mask = (torch.arange(T)[None] < lens[:, None]).float()[..., None]
-        vm = vv * mask
+        live = (torch.arange(T)[None] < lens[:, None])[..., None]
+        vm = torch.where(live, vv, torch.zeros_like(vv))          # frames behind lens are never read (they may hold anything)
         left = (ksize - 1) // 2
         xp = F.pad(vm.transpose(1, 2), (left, ksize - 1 - left))
         fs = F.conv1d(xp, w.view(D, 1, ksize), None, groups=D).transpose(1, 2)
-        r = ((fs + vm) * mask).reshape(B * T, D)
+        r = torch.where(live, fs + vm, torch.zeros_like(vm)).reshape(B * T, D)
         if accumulate:
             out.add_(r)
         else:

@@ -623,7 +623,7 @@ __global__ __launch_bounds__(256) void f32_attn_prefill_kernel(const float* __re
   // klen == NULL: causal decoder prompt, keys [kstart[b], s]; else bidirectional with key padding (SANM encoder,
   // SenseVoice.py:209-228): every query sees keys [0, klen[b])
   const int k_lo = klen ? 0 : kstart[b];
-  const int k_hi = klen ? klen[b] : s + 1;
+  const int k_hi = klen ? min(klen[b], S) : s + 1;     // (clamped like the bidirectional kernel's: no key row beyond the sequence)
   if (s < k_lo || k_hi <= k_lo || (klen && s >= k_hi)) {   // a padding position: its output is never read
     for (int i = threadIdx.x; i < REP * HD; i += 256) o[i] = 0.f;
     return;
@@ -670,6 +670,11 @@ __global__ __launch_bounds__(64 * F32_DECODE_NW) void f32_attn_decode_kernel(con
   const int LD = (H + 2 * G) * HD, Wd = G * HD;
   int* six = (int*)(smem + f32_attn_lds_floats<REP, F32_DECODE_NW>(kst));
   const int k_lo = kstart[m], k_hi = lens[m];
+  if (k_hi <= k_lo) {                                  // no visible key (workgroup-uniform): zeros, like the prefill kernel's padding rows
+    float* o = out + (size_t)m * (H * HD) + g * REP * HD;
+    for (int i = threadIdx.x; i < REP * HD; i += 64 * F32_DECODE_NW) o[i] = 0.f;
+    return;
+  }
   for (int i = k_lo + threadIdx.x; i < k_hi; i += 64 * F32_DECODE_NW) six[i] = index[(size_t)m * ctx + i];
   __syncthreads();
   f32_attn_group<REP, F32_DECODE_NW, F32_DECODE_VPRE>(qkv + (size_t)m * LD + g * REP * HD, k_lo, k_hi, scale, out + (size_t)m * (H * HD) + g * REP * HD, smem, kst,
@@ -970,9 +975,9 @@ extern "C" int tasu_f32_gemm_resid_rmsnorm(const float* A, int lda, const float*
   if (!f32_gemm_args_ok(A, lda, W, ldw, x, ldx, M, N, K) || !norm_w || !y) return TASU_ERR_ARG;
   const int ksplit = f32_ksplit(M, N, K, workspace, workspace_floats);
   if (ksplit == 1) {                                  // (whole-K tiles: the prompt pass) GEMM, then the norm
+    if (ldx != N) return TASU_ERR_ARG;                // (f32_rmsnorm_kernel reads dense rows; refused before anything is launched)
     const int rc = f32_gemm_launch(A, lda, W, ldw, x, ldx, bias, resid, M, N, K, 0, 1, workspace, workspace_floats, (hipStream_t)stream);
     if (rc) return rc;
-    if (ldx != N) return TASU_ERR_ARG;
     TASU_LAUNCH(f32_rmsnorm_kernel, dim3(M), dim3(1024), 0, (hipStream_t)stream, x, norm_w, y, N, eps);
     return TASU_OK;
   }

@@ -12,13 +12,10 @@ import math
 import numpy as np
 import torch
 
+from .model import rup
 from .ops import GEMM_BF16, GEMM_RESID
 
 HD = 128
-
-
-def rup(x, m):
-    return (x + m - 1) // m * m
 
 
 class EncoderWeights:

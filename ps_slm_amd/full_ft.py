@@ -29,6 +29,8 @@ fp32 transposed copies of the dgrads are redone in place and the fp32 fragment-o
 import numpy as np
 import torch
 
+from .model import rup
+
 HD = 128
 PRE = "llm."
 EMBED_KEY = PRE + "model.embed_tokens.weight"
@@ -36,10 +38,6 @@ HEAD_KEY = PRE + "lm_head.weight"
 NORM_KEY = PRE + "model.norm.weight"
 LAYER_ORDER = ("wd", "wgu", "ln2", "wo", "wqkv", "bqkv", "ln1")     # completion order of one layer's gradients
 F32_TENSORS = ("ln1", "ln2")                                         # read from the fp32 masters; the others from the bf16 image
-
-
-def rup(x, m):
-    return (x + m - 1) // m * m
 
 
 def is_llm_key(k):

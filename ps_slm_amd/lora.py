@@ -20,7 +20,8 @@ read dy / xd K-major as they lie (tasu_gemm_tn_rank), fp32, straight into the bu
 flat fp32 bucket (master, grad, Adam m / v, bf16 image), a layer's tensors contiguous and the layers in the order the backward
 completes them (last layer first): AdamW stays one launch, the gradient exchange gets one range per span of layers.  Nothing
 of the forward is recomputed: the operands [x | us] and every member's dropped input are kept per layer.  Decode runs on merged
-weights (merged_llm).  DESIGN.md 4g has the measurements.
+weights (merged_llm).  DESIGN.md 4g has the measurements.  The decoder layer itself is spelt once, in ps_slm_amd/train_bf16.py
+(layer_fwd / layer_bwd): LoraRunner below is what it asks, per group, for operand, weight and contraction length.
 
 use_fp16 = false: generate() and the eval-mode forward run on fp32 merged weights W_f32 + s B A (merged_llm_f32): +1x the decoder's
 fp32 layer weights, about 5 GB at Qwen2.5-1.5B, plus fragment-order copies of gate|up and down (~4.6 GB) at the first fp32 generate().
@@ -33,7 +34,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .ops import GEMM_F32, GEMM_RESID
+from .model import rup
+from .ops import GEMM_F32
 from .streams import side_stream
 
 HD = 128
@@ -41,10 +43,6 @@ TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down
 _PARENT = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn",
            "gate_proj": "mlp", "up_proj": "mlp", "down_proj": "mlp"}
 GROUPS = (("qkv", ("q_proj", "k_proj", "v_proj")), ("o", ("o_proj",)), ("gu", ("gate_proj", "up_proj")), ("down", ("down_proj",)))
-
-
-def rup(x, m):
-    return (x + m - 1) // m * m
 
 
 @dataclass
@@ -230,6 +228,15 @@ class LoraParams:
     def seed_dropout(self, seed, step=0):
         self.rng.copy_(torch.tensor([int(seed), int(step)], dtype=torch.int64))
 
+    def drop_on(self, training):
+        """Whether a forward in this mode draws dropout masks."""
+        return bool(training and self.cfg.lora_dropout > 0.0)
+
+    @staticmethod
+    def sid(l, t):
+        """Stream id of (layer, target)'s mask in the counter-based generator (csrc/lora.hip)."""
+        return l * 8 + TARGETS.index(t)
+
     def _refresh_table(self):
         """The copies of refresh_working_copies as the device table of tasu_lora_refresh (addresses are fixed for the model's life)."""
         import struct
@@ -281,7 +288,6 @@ def merged_llm(model):
     if lp._merged is not None and lp._merged_version == lp.version and len(lp._merged.layers) == len(base.layers):
         return lp._merged
     s, ops, p = lp.cfg.scaling, model.ops, lp.proj.p
-    from .ops import GEMM_F32
     bf = torch.bfloat16
 
     def delta(l, t):
@@ -378,8 +384,10 @@ def merged_llm_f32(model):
 
 
 class LoraRunner:
-    """The adapted decoder layer: forward and backward of one layer with the low-rank branches in place.  Called by
-    TasuModel.forward_llm / backward_llm when ``model.lora`` is set; uses the model's named workspace buffers.
+    """The low-rank branches of the adapted decoder layer.  The layer itself is spelt once for every recipe (ps_slm_amd/train_bf16.py:
+    layer_fwd / layer_bwd); this runner is its adapter collaborator: per group it hands out the K-extended operand, weight and
+    contraction length (group), runs the members' rank activations (us) and their backward (bwd), and owns the side stream of the
+    weight-gradient chains (_wait_side / join).  Uses the model's named workspace buffers.
 
     Forward: per adapted group ONE GEMM  y = [x | us] [W | B]^T  with K extended by the members' ranks (padded to 128): the
     producers of x (RMSNorm, the SwiGLU epilogue; a row copy for the attention output) write into the head of the operand, the
@@ -398,6 +406,7 @@ class LoraRunner:
         # fork / join of the capturing stream).  Its workgroup counts (96-560) leave most of the chip to the main stream's GEMMs.
         self.side = side_stream(model.device, "adapter weight gradients", owner=self)              # on its own hardware queue (ps_slm_amd/streams.py); None on the CPU double
         self._side_done = {}                               # group -> event: the side chain that read this group's buffers has finished
+        self.members = dict(self.lp.groups)                # adapted group -> its adapted members
 
     # ---- workspace
     def _zbuf(self, name, shape):
@@ -424,12 +433,6 @@ class LoraRunner:
         import os
         return hasattr(ops, "lora_apply_group") and os.environ.get("TASU_LORA_GROUPED", "1") != "0"
 
-    def _drop_on(self, training):
-        return bool(training and self.lp.cfg.lora_dropout > 0.0)
-
-    def _sid(self, l, t):
-        return l * 8 + TARGETS.index(t)
-
     def _ax(self, gname, M):
         """The group's K-extended activation operand, kept per layer: [L, M, kext] = [x | us of every member | zero pad]."""
         return self._zbuf("lora_ax_" + gname, (self.m.geo.llm_layers, M, self.lp.kext[gname]))
@@ -441,6 +444,52 @@ class LoraRunner:
     def _us_view(self, gname, l, M, nt):
         K = self.lp.kbase[gname]
         return self._ax(gname, M)[l][:, K:K + nt * self.lp.rp]
+
+    # ---- what the layer asks per group (train_bf16.layer_fwd / layer_bwd)
+    def group(self, gname, l, M, x, w, K):
+        """(GEMM operand, its head: where the producer of x writes, weight, contraction length, adapted members) of a group's Linear:
+        [x | us] [W | B]^T at K = kext, or -- no member adapted -- the frozen x W^T."""
+        ts = self.members.get(gname)
+        if not ts:
+            return x, x, w, K, ()
+        a = self._ax(gname, M)[l]
+        return a, a[:, :K], self.lp.wext[(l, gname)], self.lp.kext[gname], ts
+
+    def us(self, l, gname, targets, M, x, drop, norm=None):
+        """The members' rank activations from x, the group's input [M, in]; with dropout from every member's own dropped copy, kept
+        per layer.  ``norm`` = (residual stream, norm weight, rstd) where x is an RMSNorm's output: the masks are applied to the
+        norm's fp32 output, evaluated once for the group where the operator set has the group kernel."""
+        if not targets:
+            return
+        if not drop:
+            return self.group_us(l, gname, targets, M, lambda t: x)
+        lp, ops, p, width = self.lp, self.m.ops, self.lp.cfg.lora_dropout, x.shape[1]
+        if norm is not None and len(targets) > 1 and self._grouped(ops):
+            dsts = {t: self._xin(t, M, width)[l] for t in targets}
+            ops.lora_dropout_norm_group(*norm, [dsts[t] for t in targets], M, width, p, lp.rng, [lp.sid(l, t) for t in targets])
+            return self.group_us(l, gname, targets, M, dsts.get)
+
+        def dropped(t):
+            dst = self._xin(t, M, width)[l]
+            if norm is not None:
+                ops.lora_dropout_norm(*norm, dst, M, width, p, lp.rng, lp.sid(l, t))
+            else:
+                ops.lora_dropout(x, dst, p, lp.rng, lp.sid(l, t))
+            return dst
+        self.group_us(l, gname, targets, M, dropped)
+
+    def bwd(self, l, gname, dy, width, M, K, dx_base, drop, shared=None):
+        """group_bwd where the group is adapted.  The input its members' adapters saw in the forward: their dropped copies, else
+        ``shared`` (a tensor the step keeps anyway), else the head [M, K] of the group's forward operand."""
+        ts = self.members.get(gname)
+        if not ts:
+            return
+        if drop:
+            xd_of = lambda t: self._xin(t, M, K)[l]
+        else:
+            x = shared if shared is not None else self._ax(gname, M)[l][:, :K]
+            xd_of = lambda t: x
+        self.group_bwd(l, gname, ts, dy, width, M, xd_of, dx_base, drop)
 
     # ---- forward of one group: the rank activations of every member into the tail of the group's operand
     def group_us(self, l, gname, targets, M, xd_of):
@@ -472,14 +521,14 @@ class LoraRunner:
         if nt > 1 and r <= 64 and rp == 64 and self._grouped(ops):       # the group's members in one launch each (the same bits as the loop below)
             ops.gemm_rank_group([dy[:, lp.cols[t]:lp.cols[t] + lp.dims[t][1]] for t in targets], [lp.bts[(l, t)] for t in targets], dus, M, r,
                                 [lp.dims[t][1] for t in targets])
-            ops.lora_apply_group(dx_base, dus, [lp.at[(l, t)] for t in targets], M, inn, rp, [self._sid(l, t) for t in targets],
+            ops.lora_apply_group(dx_base, dus, [lp.at[(l, t)] for t in targets], M, inn, rp, [lp.sid(l, t) for t in targets],
                                  p=p if drop else 0.0, rng=lp.rng)
         else:
             for t, du_t in zip(targets, dus):
                 i, o = lp.dims[t]
                 c0 = lp.cols[t]
                 self.rank(dy[:, c0:c0 + o], lp.bts[(l, t)], du_t, M, r, o)             # du = bf16(dy (sB))              [M, r]
-                ops.lora_apply(dx_base, du_t, lp.at[(l, t)], M, i, rp, p=p if drop else 0.0, rng=lp.rng, sid=self._sid(l, t))
+                ops.lora_apply(dx_base, du_t, lp.at[(l, t)], M, i, rp, p=p if drop else 0.0, rng=lp.rng, sid=lp.sid(l, t))
         # weight gradients: dB_t = dy_t^T us_t [out, r],  dA_t = du_t^T xd_t [r, in]  (K = the M rows).  The big operands (dy, xd) are
         # read K-major as they are (tasu_gemm_tn_rank: hardware transpose reads); only the rank-sized ones are transposed
         # (zero-padded to Mp = 64-row multiples; the padding rows of dy / xd are never read when M itself is a multiple of 64).
@@ -532,115 +581,3 @@ class LoraRunner:
         """End of the decoder's backward: every weight gradient is in the bucket (and a capturing stream has its forks back)."""
         for g in list(self._side_done):
             self._wait_side(g)
-
-    # ---- one decoder layer, forward (modeling_qwen2.py's Qwen2DecoderLayer with every adapted Linear = base + low-rank branch)
-    def layer_fwd(self, st, l, w, bufs, drop):
-        m, lp, ops, geo = self.m, self.lp, self.m.ops, self.m.geo
-        B, S, M = st.B, st.S, st.M
-        D, I, H, G = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads
-        scale, eps, p = HD ** -0.5, geo.rms_eps, lp.cfg.lora_dropout
-        xs, rstd, qkv, ao, lse, gu, xn, act, cos, sin = (bufs[k] for k in ("xs", "rstd", "qkv", "ao", "lse", "gu", "xn", "act", "cos", "sin"))
-        x_in, x_mid, x_out = xs[2 * l], xs[2 * l + 1], xs[2 * l + 2]
-        groups = dict(lp.groups)
-        sid = lambda t: self._sid(l, t)
-
-        def dropped_norm(x, wn, rs, targets):               # member -> its own dropped copy of the norm's fp32 output, kept per layer
-            if len(targets) > 1 and self._grouped(ops):      # the norm evaluated once for the group, every member's mask applied to it
-                dsts = {t: self._xin(t, M, D)[l] for t in targets}
-                ops.lora_dropout_norm_group(x, wn, rs, [dsts[t] for t in targets], M, D, p, lp.rng, [sid(t) for t in targets])
-                return lambda t: dsts[t]
-
-            def f(t):
-                dst = self._xin(t, M, D)[l]
-                ops.lora_dropout_norm(x, wn, rs, dst, M, D, p, lp.rng, sid(t))
-                return dst
-            return f
-
-        def dropped(src, width):
-            def f(t):
-                dst = self._xin(t, M, width)[l]
-                ops.lora_dropout(src, dst, p, lp.rng, sid(t))
-                return dst
-            return f
-
-        # ---- attention block
-        if "qkv" in groups:
-            a = self._ax("qkv", M)[l]
-            x1 = a[:, :D]                                   # the norm writes straight into the head of the operand
-            ops.rmsnorm_fwd(x_in, w["ln1"], x1, rstd[2 * l], eps)
-            self.group_us(l, "qkv", groups["qkv"], M, dropped_norm(x_in, w["ln1"], rstd[2 * l], groups["qkv"]) if drop else (lambda t: x1))
-            ops.gemm_qkv_rope(a, lp.wext[(l, "qkv")], w["bqkv"], qkv[l], cos, sin, M, H, G, lp.kext["qkv"])
-        else:
-            ops.rmsnorm_fwd(x_in, w["ln1"], xn, rstd[2 * l], eps)
-            ops.gemm_qkv_rope(xn, w["wqkv"], w["bqkv"], qkv[l], cos, sin, M, H, G, D)
-        ops.attn_fwd(qkv[l], None, st.dev["key_mask"], ao[l], lse[l], B, S, H, G, scale, True)
-        if "o" in groups:
-            a = self._ax("o", M)[l]
-            ops.copy_rows(ao[l], a, M, H * HD)              # (the attention kernels write a dense [M, H * 128])
-            self.group_us(l, "o", groups["o"], M, dropped(ao[l], H * HD) if drop else (lambda t: ao[l]))
-            ops.gemm(a, lp.wext[(l, "o")], x_mid, M, D, lp.kext["o"], resid=x_in, mode=GEMM_RESID)
-        else:
-            ops.gemm(ao[l], w["wo"], x_mid, M, D, H * HD, resid=x_in, mode=GEMM_RESID)
-        # ---- MLP block: the SwiGLU epilogue writes act into the head of the down projection's operand
-        ad = self._ax("down", M)[l] if "down" in groups else None
-        act_l = ad[:, :I] if ad is not None else act
-        if "gu" in groups:
-            a = self._ax("gu", M)[l]
-            x2 = a[:, :D]
-            ops.rmsnorm_fwd(x_mid, w["ln2"], x2, rstd[2 * l + 1], eps)
-            self.group_us(l, "gu", groups["gu"], M, dropped_norm(x_mid, w["ln2"], rstd[2 * l + 1], groups["gu"]) if drop else (lambda t: x2))
-            ops.gemm_gate_up_swiglu(a, lp.wext[(l, "gu")], gu[l], act_l, M, I, lp.kext["gu"])
-        else:
-            ops.rmsnorm_fwd(x_mid, w["ln2"], xn, rstd[2 * l + 1], eps)
-            ops.gemm_gate_up_swiglu(xn, w["wgu"], gu[l], act_l, M, I, D)
-        if "down" in groups:
-            self.group_us(l, "down", groups["down"], M, dropped(act_l, I) if drop else (lambda t: act_l))
-            ops.gemm(ad, lp.wext[(l, "down")], x_out, M, D, lp.kext["down"], resid=x_mid, mode=GEMM_RESID)
-        else:
-            ops.gemm(act_l, w["wd"], x_out, M, D, I, resid=x_mid, mode=GEMM_RESID)
-
-    # ---- one decoder layer, backward: the frozen recipe's dgrad chain + every adapter's dgrad and weight gradients
-    def layer_bwd(self, st, l, w, bufs, drop):
-        m, lp, ops, geo, d = self.m, self.lp, self.m.ops, self.m.geo, st.dev
-        B, S, M = st.B, st.S, st.M
-        D, I, H, G = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads
-        LDQ, scale = (H + 2 * G) * HD, HD ** -0.5
-        dx, dxb, dn, dact, dgu, dao, delta, dqkv, dkp, dvp = (bufs[k] for k in ("dx", "dxb", "dn", "dact", "dgu", "dao", "delta", "dqkv", "dkp", "dvp"))
-        xs, rstd, cos, sin = d["xs"], d["rstd"], d["cos"], d["sin"]
-        x_in, x_mid = xs[2 * l], xs[2 * l + 1]
-        groups = dict(lp.groups)
-
-        def stored(gname, width, shared=None):
-            """member -> the input its adapter saw in the forward: its dropped copy, or the head of the group's forward operand."""
-            if drop:
-                return lambda t: self._xin(t, M, width)[l]
-            if shared is not None:
-                return lambda t: shared
-            buf = self._ax(gname, M)[l][:, :width]
-            return lambda t: buf
-
-        # The weight-gradient chains on the side stream read the group's output gradient IN PLACE (dxb, dgu, dqkv: no transposed
-        # copy, tasu_gemm_tn_rank): the main stream waits for a group's chain right before the kernel that rewrites that buffer.
-        if "down" in groups:
-            ops.gemm(dxb, w["wd_t"], dact, M, I, D)
-            self.group_bwd(l, "down", groups["down"], dxb, D, M, stored("down", I), dact, drop)
-            self._wait_side("gu")                                     # (the previous layer's chain over dgu)
-            ops.swiglu_bwd(dact, d["gu"][l], dgu, M, I)
-        else:
-            self._wait_side("gu")
-            ops.gemm_dswiglu(dxb, w["wd_t"], d["gu"][l], dgu, dact, M, I, D)
-        ops.gemm(dgu, w["wgu_t"], dn, M, D, 2 * I)
-        if "gu" in groups:
-            self.group_bwd(l, "gu", groups["gu"], dgu, 2 * I, M, stored("gu", D), dn, drop)
-        self._wait_side("down")                                       # its chain read dxb
-        ops.rmsnorm_bwd(dn, x_mid, w["ln2"], rstd[2 * l + 1], dx, dxb, True)
-        ops.gemm(dxb, w["wo_t"], dao, M, H * HD, D)
-        if "o" in groups:
-            self.group_bwd(l, "o", groups["o"], dxb, D, M, stored("o", H * HD, shared=d["ao"][l]), dao, drop)
-        self._wait_side("qkv")                                        # (the previous layer's chain over dqkv)
-        ops.attn_bwd_fused(d["qkv"][l], d["key_mask"], dao, d["ao"][l], d["lse"][l], delta, cos, sin, dqkv, dkp, dvp, B, S, H, G, scale, True)
-        ops.gemm(dqkv, w["wqkv_t"], dn, M, D, LDQ)
-        if "qkv" in groups:
-            self.group_bwd(l, "qkv", groups["qkv"], dqkv, LDQ, M, stored("qkv", D), dn, drop)
-        self._wait_side("o")                                          # its chain read dxb
-        ops.rmsnorm_bwd(dn, x_in, w["ln1"], rstd[2 * l], dx, dxb, True)

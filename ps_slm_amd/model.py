@@ -1,7 +1,8 @@
 """Device-resident TASU model: weights laid out for the gfx950 kernels + the hand-scheduled forward/backward of
 the alignment training step (no autograd tape, no tracing compiler: the graph is fixed because the LLM and the
 encoder are frozen -- Multitask/scripts/finetune_deespeed_sensevoice.sh:44,84 -- so backward is dgrad-only
-through the decoder and wgrad only for the 6 projector tensors).
+through the decoder and wgrad only for the 6 projector tensors).  Here: weights, bucket layout, host prep, projector and graph
+plumbing; the decoder part of the bf16 step (forward_llm / backward_llm delegate) is ps_slm_amd/train_bf16.py, next to train_fp32.py.
 
 Reference arithmetic being replaced:
   slam_model_asr.forward            Multitask/model/ps-slm.py:411-537
@@ -30,7 +31,7 @@ import torch
 
 from .graphs import GraphCache
 from .merge import build_merge_plan
-from .ops import GEMM_BF16, GEMM_F32, GEMM_RESID, LN_BWD_SPLIT
+from .ops import GEMM_F32, LN_BWD_SPLIT
 
 HD = 128
 
@@ -1132,129 +1133,14 @@ class TasuModel:
         if on_ready is not None:
             on_ready(0, self.proj_end)
 
+    # ---- the decoder part of the bf16 step lives in ps_slm_amd/train_bf16.py (one layer forward, one layer backward for every recipe)
     def forward_llm(self, st: StepState, compute_loss=True, need_backward=True, logits_rows="all"):
-        ops, geo, llm = self.ops, self.geo, self.llm
-        B, S, M = st.B, st.S, st.M
-        D, I, H, G, V = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab
-        Spad, Vp, LDQ = st.plan.Spad, rup(V, 64), (H + 2 * G) * HD
-        scale = HD ** -0.5
-        L = geo.llm_layers
-        d = st.dev
-        bf, f32 = torch.bfloat16, torch.float32
-        xs = self._buf("xs", (2 * L + 1, M, D), f32)          # x_in[l] = xs[2l], x_mid[l] = xs[2l+1], final = xs[2L]
-        ops.embed_merge(llm.embed, d["y2"], d["kind"], d["idx"], xs[0], M, D)
-        cos = self._buf("cos", (M, HD // 2), f32)
-        sin = self._buf("sin", (M, HD // 2), f32)
-        ops.rope_table(d["pos"], cos, sin, HD, geo.rope_theta)
-        rstd = self._buf("rstd", (2 * L + 1, M), f32)
-        qkv = self._buf("qkv", (L, M, LDQ), bf)
-        ao = self._buf("ao", (L, M, H * HD), bf)
-        lse = self._buf("lse", (L, B * H * Spad), f32)
-        gu = self._buf("gu", (L, M, 2 * I), bf)
-        xn = self._buf("xn_llm", (M, D), bf)
-        act = self._buf("act", (M, I), bf)
-        lora = self._lora_run
-        ft = self.full_ft
-        # full fine-tuning keeps the GEMM operands of every layer for the weight gradients (the normed inputs and the SwiGLU output;
-        # the frozen step overwrites one buffer), and runs no compact tail: the last layer's MLP weights want all rows' operands in
-        # the same [M, .] form as every other layer's
-        keep = ft is not None and need_backward
-        if keep:
-            xn_l = self._buf("ft_xn", (2 * L, M, D), bf)
-            act_l = self._buf("ft_act", (L, M, I), bf)
-            d.update(ft_xn=xn_l, ft_act=act_l)
-        tail = bool(self.tail_rows and compute_loss and need_backward and not self.keep_logits and logits_rows != "none"
-                    and "lab_rows" in d and st.nLp > 0 and lora is None and ft is None)
-        drop = lora is not None and lora._drop_on(self.training)
-        if drop:
-            ops.rng_advance(self.lora.rng)                     # new masks for this micro-step (a launch: graph replays advance too)
-        st.lora_drop = drop
-        fb = dict(xs=xs, rstd=rstd, qkv=qkv, ao=ao, lse=lse, gu=gu, xn=xn, act=act, cos=cos, sin=sin)
-        for l, w in enumerate(llm.layers):
-            if lora is not None:
-                lora.layer_fwd(st, l, w, fb, drop)
-                continue
-            x_in, x_mid, x_out = xs[2 * l], xs[2 * l + 1], xs[2 * l + 2]
-            if keep:                                           # this layer's own operand buffers
-                xn, act = xn_l[2 * l], act_l[l]
-            ops.rmsnorm_fwd(x_in, w["ln1"], xn, rstd[2 * l], geo.rms_eps)
-            ops.gemm_qkv_rope(xn, w["wqkv"], w["bqkv"], qkv[l], cos, sin, M, H, G, D)      # bias + RoPE in the GEMM's epilogue
-            ops.attn_fwd(qkv[l], None, d["key_mask"], ao[l], lse[l], B, S, H, G, scale, True)
-            ops.gemm(ao[l], w["wo"], x_mid, M, D, H * HD, resid=x_in, mode=GEMM_RESID)
-            if tail and l == L - 1:
-                # the last layer's MLP on the nLp labelled rows (compact operands; row gathers by the plan's index)
-                n = st.nLp
-                xn_t = self._buf("xn_tail", (n, D), bf)
-                rstd_t = self._buf("rstd_tail", (n,), f32)
-                ops.rmsnorm_fwd_rows(x_mid, d["lab_rows"], w["ln2"], xn_t, rstd_t, geo.rms_eps)
-                gu_t = self._buf("gu_tail", (n, 2 * I), bf)
-                act_t = self._buf("act_tail", (n, I), bf)
-                ops.gemm_gate_up_swiglu(xn_t, w["wgu"], gu_t, act_t, n, I, D)
-                xmid_t = self._buf("xmid_tail", (n, D), f32)
-                ops.embed_rows(x_mid, d["lab_rows0"], xmid_t, n, D)
-                xout_t = self._buf("xout_tail", (n, D), f32)
-                ops.gemm(act_t, w["wd"], xout_t, n, D, I, resid=xmid_t, mode=GEMM_RESID)
-                d.update(rstd_tail=rstd_t, gu_tail=gu_t, xout_tail=xout_t)
-                continue
-            if keep:
-                xn = xn_l[2 * l + 1]
-            ops.rmsnorm_fwd(x_mid, w["ln2"], xn, rstd[2 * l + 1], geo.rms_eps)
-            ops.gemm_gate_up_swiglu(xn, w["wgu"], gu[l], act, M, I, D)          # gate|up projection + SwiGLU epilogue
-            ops.gemm(act, w["wd"], x_out, M, D, I, resid=x_mid, mode=GEMM_RESID)
-        d.update(xs=xs, cos=cos, sin=sin, rstd=rstd, qkv=qkv, ao=ao, lse=lse, gu=gu)
-        if logits_rows == "none":                              # decode prefill: the caller projects the last rows only
-            return
-        if compute_loss and need_backward and not self.keep_logits:
-            return self._loss_on_labelled_rows(st)
-        if keep:
-            xn = self._buf("xn_llm", (M, D), bf)               # (not the last layer's kept operand)
-        ops.rmsnorm_fwd(xs[2 * L], llm.norm, xn, rstd[2 * L], geo.rms_eps)
-        logits = self._buf("logits", (M, Vp), bf)
-        ops.gemm(xn, llm.head, logits, M, V, D)
-        d.update(logits=logits, xn_head=xn)
-        if not compute_loss:
-            return
-        row_loss = self._buf("row_loss", (M,), f32)
-        row_hit = self._buf("row_hit", (M,), torch.int32)
-        # per-row argmax (the reference's `preds`, ps-slm.py:533) only matters at labelled rows for the accuracy; the kernel
-        # skips the scan of ignored rows when no argmax buffer is passed, which the training step does
-        row_arg = None if need_backward else self._buf("row_arg", (M,), torch.int32)
-        if need_backward and not self.keep_logits:
-            dlogits = logits                                   # overwrite in place (throughput mode)
-        elif need_backward:
-            dlogits = self._buf("dlogits", (M, Vp), bf)
-        else:
-            dlogits = None
-        ops.ce_fwd_bwd(logits, d["shift_labels"], M, V, row_loss, row_hit, row_arg, dlogits, d["inv_count"])
-        res = self._buf("loss_out", (4,), f32)
-        ops.ce_reduce(row_loss, row_hit, d["shift_labels"], M, res)
-        d.update(dlogits=dlogits, loss_out=res, row_arg=row_arg)
+        from .train_bf16 import forward_llm
+        return forward_llm(self, st, compute_loss, need_backward, logits_rows)
 
     def _loss_on_labelled_rows(self, st: StepState):
-        """Throughput form of the loss head (training step, ``keep_logits=False``): the shifted CE ignores every position
-        without a label (loss_utils.py:49-71, ignore_index -100), so final norm -> lm_head -> CE -> dlogits run over the
-        labelled rows only, gathered into a compact [nLp, D] operand (half of the 4096 rows of the benchmark batch, whose
-        prompt and audio positions carry no label).  Loss, accuracy and every gradient equal the full-materialisation path's
-        (rows without a label have dlogits == 0 there); ``outputs.logits`` does not exist in this mode."""
-        ops, geo, llm, d = self.ops, self.geo, self.llm, st.dev
-        D, V, L = geo.llm_dim, geo.llm_vocab, geo.llm_layers
-        Vp, n = rup(V, 64), st.nLp
-        bf, f32 = torch.bfloat16, torch.float32
-        xn_c = self._buf("xn_lab", (n, D), bf)
-        rstd_c = self._buf("rstd_lab", (n,), f32)
-        if "xout_tail" in d:                                 # the last layer already produced the labelled rows compact
-            ops.rmsnorm_fwd(d["xout_tail"], llm.norm, xn_c, rstd_c, geo.rms_eps)
-        else:
-            ops.rmsnorm_fwd_rows(d["xs"][2 * L], d["lab_rows"], llm.norm, xn_c, rstd_c, geo.rms_eps)
-        logits = self._buf("logits", (n, Vp), bf)
-        ops.gemm(xn_c, llm.head, logits, n, V, D)
-        row_loss = self._buf("row_loss", (n,), f32)
-        row_hit = self._buf("row_hit", (n,), torch.int32)
-        ops.ce_fwd_bwd(logits, d["lab_compact"], n, V, row_loss, row_hit, None, logits, d["inv_count"])   # dlogits in place
-        res = self._buf("loss_out", (4,), f32)
-        ops.ce_reduce(row_loss, row_hit, d["lab_compact"], n, res)
-        d.update(dlogits=logits, loss_out=res, row_arg=None, rstd_lab=rstd_c, labelled_only=True, xn_head=xn_c)
-        d.pop("logits", None)
+        from .train_bf16 import loss_on_labelled_rows
+        return loss_on_labelled_rows(self, st)
 
     # ------------------------------------------------------------------------------------------ backward
     def backward(self, st: StepState, on_ready=None, w1_chunks=1):
@@ -1266,20 +1152,8 @@ class TasuModel:
             self.backward_embed(st, on_ready)
 
     def _head_wgrad(self, st, dst=None):
-        """use_emb with tied embeddings: the lm_head's weight gradient dW = dlogits^T h is the second term of the table's gradient
-        (h: the final-normed rows that fed the lm_head GEMM -- the compact labelled rows in the throughput mode).  fp32, on the MFMA
-        GEMM behind the transposes the projector's dW1 uses, straight into (overwriting) the table's range of the bucket; rows
-        without a label and the padding rows have dlogits == 0 / h == 0."""
-        ops, geo, d = self.ops, self.geo, st.dev
-        V, D, Vp = geo.llm_vocab, geo.llm_dim, rup(geo.llm_vocab, 64)
-        n = st.nLp if d.get("labelled_only") else st.M
-        npad = rup(n, 64)
-        dl_t = self._buf("emb_dl_t", (Vp, npad), torch.bfloat16)
-        h_t = self._buf("emb_h_t", (D, npad), torch.bfloat16)
-        ops.transpose(d["dlogits"], dl_t, n, Vp, npad, Vp)
-        ops.transpose(d["xn_head"], h_t, n, D, npad, D)
-        # (dst: the untied lm_head's own range when the whole decoder trains -- the same product)
-        ops.gemm(dl_t, h_t, self.embed_view(self.proj.g) if dst is None else dst, V, D, npad, mode=GEMM_F32)
+        from .train_bf16 import head_wgrad
+        return head_wgrad(self, st, dst)
 
     def backward_embed(self, st, on_ready=None):
         """use_emb: the lookup term of the table's gradient -- every text row of dx = d(loss)/d(inputs_embeds) added into the row of
@@ -1301,105 +1175,8 @@ class TasuModel:
             on_ready(self._embed_tail_lo, self.embed_range[1])     # (with the alignment gap in front of it: grad_ranges)
 
     def backward_llm(self, st: StepState, span=None):
-        """lm_head dgrad, final norm, 28 decoder layers (dgrad only: the LLM is frozen).  Leaves d(loss)/d(inputs_embeds)
-        in the fp32 workspace buffer ``dx``.  ``span`` = (hi, lo): only layers hi - 1 .. lo (the loss head with the span that
-        starts at the last layer) -- the adapters' gradient exchange cuts the backward into such spans (run_backward)."""
-        ops, geo, llm = self.ops, self.geo, self.llm
-        B, S, M = st.B, st.S, st.M
-        D, I, H, G, V = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab
-        Spad, Vp, LDQ = st.plan.Spad, rup(V, 64), (H + 2 * G) * HD
-        scale = HD ** -0.5
-        L = geo.llm_layers
-        d = st.dev
-        bf, f32 = torch.bfloat16, torch.float32
-        xs, rstd, cos, sin = d["xs"], d["rstd"], d["cos"], d["sin"]
-        dx = self._buf("dx", (M, D), f32)
-        dxb = self._buf("dxb", (M, D), bf)
-        dn = self._buf("dn", (M, D), bf)                       # gradient wrt a normed activation
-        dact = self._buf("dact", (M, I), bf)
-        dgu = self._buf("dgu", (M, 2 * I), bf)
-        dao = self._buf("dao", (M, H * HD), bf)
-        delta = self._buf("delta", (B * H * Spad,), f32)
-        dqkv = self._buf("dqkv", (M, LDQ), bf)
-        dkp = self._buf("dkp", (M, H * HD), f32)
-        dvp = self._buf("dvp", (M, H * HD), f32)
-        l_hi, l_lo = span if span is not None else (L, 0)
-        # lm_head dgrad (K = Vpad: dlogits pad columns are zero) and final norm
-        ft = self.full_ft
-        if l_hi == L and self.embed_base is not None and geo.tied:
-            self._head_wgrad(st)
-        elif l_hi == L and ft is not None:
-            self._head_wgrad(st, ft.view(self.proj.g, "head"))
-        if l_hi < L:
-            pass                                               # a later span: the loss head ran with the first one
-        elif d.get("labelled_only"):
-            dn_c = self._buf("dn_lab", (st.nLp, D), bf)
-            # [nLp, D] outputs in 128 x 192 tiles behind K = Vp: when they cover at most half of the 256 CUs the K range is
-            # split so that every CU works (2048 labelled rows x 1536: 128 tiles x 2 ranges)
-            tiles = ((st.nLp + 127) // 128) * ((D + 191) // 192)
-            ksplit = max(1, min(256 // tiles, 8))
-            while ksplit > 1 and Vp % (64 * ksplit):
-                ksplit -= 1
-            if ksplit > 1 and D % 4 == 0:
-                ws = self._buf("dn_lab_slabs", (ksplit, st.nLp, D), f32)
-                ops.gemm_splitk(d["dlogits"], llm.head_t, dn_c, st.nLp, D, Vp, ksplit, ws)
-            else:
-                ops.gemm(d["dlogits"], llm.head_t, dn_c, st.nLp, D, Vp)
-            if "xout_tail" in d:
-                # final norm and the last layer's MLP on the compact rows; the post-attention norm's backward scatters the result
-                # (+ the rows' residual gradient) back to all M rows for that layer's attention backward
-                n, w = st.nLp, llm.layers[L - 1]
-                dx_t = self._buf("dx_tail", (n, D), f32)
-                dxb_t = self._buf("dxb_tail", (n, D), bf)
-                ops.rmsnorm_bwd(dn_c, d["xout_tail"], llm.norm, d["rstd_lab"], dx_t, dxb_t, False)
-                dact_t = self._buf("dact_tail", (n, I), bf)
-                dgu_t = self._buf("dgu_tail", (n, 2 * I), bf)
-                ops.gemm_dswiglu(dxb_t, w["wd_t"], d["gu_tail"], dgu_t, dact_t, n, I, D)
-                ops.gemm(dgu_t, w["wgu_t"], dn_c, n, D, 2 * I)
-                ops.rmsnorm_bwd_rows_resid(dn_c, xs[2 * L - 1], w["ln2"], d["rstd_tail"], d["lab_slot"], dx_t, dx, dxb)
-            else:
-                if ft is not None:                             # model.norm.weight: compact dy / rstd, x by the labelled rows' index
-                    ft.norm_wgrad(dn_c, xs[2 * L], d["rstd_lab"], "norm", None, src_rows=d["lab_rows"])
-                ops.rmsnorm_bwd_rows(dn_c, xs[2 * L], llm.norm, d["rstd_lab"], d["lab_slot"], dx, dxb)
-        else:
-            ops.gemm(d["dlogits"], llm.head_t, dn, M, D, Vp)
-            if ft is not None:
-                ft.norm_wgrad(dn, xs[2 * L], rstd[2 * L], "norm", None)
-            ops.rmsnorm_bwd(dn, xs[2 * L], llm.norm, rstd[2 * L], dx, dxb, False)
-        lora = self._lora_run
-        bb = dict(dx=dx, dxb=dxb, dn=dn, dact=dact, dgu=dgu, dao=dao, delta=delta, dqkv=dqkv, dkp=dkp, dvp=dvp)
-        for l in range(l_hi - 1, l_lo - 1, -1):
-            w = llm.layers[l]
-            if lora is not None:
-                lora.layer_bwd(st, l, w, bb, bool(getattr(st, "lora_drop", False)))
-                continue
-            x_in, x_mid = xs[2 * l], xs[2 * l + 1]
-            # full fine-tuning (ft; no compact tail then): every weight gradient sits next to the dgrad that consumes the same dY
-            if not (l == L - 1 and "xout_tail" in d):          # (the compact tail above has done the last layer's MLP)
-                ops.gemm_dswiglu(dxb, w["wd_t"], d["gu"][l], dgu, dact, M, I, D)
-                if ft is not None:
-                    ft.wgrad(dxb, d["ft_act"][l], "wd", l)
-                ops.gemm(dgu, w["wgu_t"], dn, M, D, 2 * I)
-                if ft is not None:
-                    ft.wgrad(dgu, d["ft_xn"][2 * l + 1], "wgu", l)
-                    ft.norm_wgrad(dn, x_mid, rstd[2 * l + 1], "ln2", l)
-                ops.rmsnorm_bwd(dn, x_mid, w["ln2"], rstd[2 * l + 1], dx, dxb, True)
-            if ft is not None:
-                ft.wgrad(dxb, d["ao"][l], "wo", l)
-            ops.gemm(dxb, w["wo_t"], dao, M, H * HD, D)
-            # delta = rowsum(dO . O), dQ, dK / dV and the rotary embedding's backward behind one entry point: the single-pass kernels
-            # for Spad <= 256 (delta inside the kernel; dkp / dvp = one fp32 partial per query head), else the tiled kernels
-            ops.attn_bwd_fused(d["qkv"][l], d["key_mask"], dao, d["ao"][l], d["lse"][l], delta, cos, sin, dqkv, dkp, dvp, B, S, H, G, scale, True)
-            if ft is not None:
-                ft.wgrad(dqkv, d["ft_xn"][2 * l], "wqkv", l)
-                ft.bias_wgrad(dqkv, "bqkv", l)                 # q|k|v bias: dqkv behind the RoPE backward
-            ops.gemm(dqkv, w["wqkv_t"], dn, M, D, LDQ)
-            if ft is not None:
-                ft.norm_wgrad(dn, x_in, rstd[2 * l], "ln1", l)
-            ops.rmsnorm_bwd(dn, x_in, w["ln1"], rstd[2 * l], dx, dxb, True)
-        if lora is not None:
-            lora.join()                                        # the adapters' weight-gradient chains (side stream) are back
-        d["dx"] = dx
+        from .train_bf16 import backward_llm
+        return backward_llm(self, st, span)
 
     def grad_ranges(self, w1_chunks=1):
         """The flat gradient bucket as the ranges backward_projector completes, in completion order:
@@ -1525,7 +1302,7 @@ class TasuModel:
         """Whether THIS step's forward draws LoRA dropout masks -- recorded on the step state by host code that runs on every
         call.  forward_llm sets the same flag, but its Python body only runs at capture time: on a hipGraph replay a fresh
         StepState would keep the default False, and a backward captured then would regenerate no masks."""
-        st.lora_drop = bool(self._lora_run is not None and self._lora_run._drop_on(self.training))
+        st.lora_drop = bool(self._lora_run is not None and self.lora.drop_on(self.training))
 
     def run_forward_text(self, st, compute_loss=True, need_backward=True):
         """forward_projector_text + forward_llm, graph-replayed when enabled."""

@@ -24,7 +24,6 @@ unmerged forward y = W x + s B (A drop(x)) and the adapters' gradients into the 
 import torch
 
 from .decode_fp32 import _gemm_ws, prompt_pass_fp32
-from .lora import TARGETS
 from .model import HD, StepState, rup
 
 
@@ -64,7 +63,7 @@ def forward_train_fp32(model, st: StepState):
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
     keep = {}
-    st.lora_drop = model.lora is not None and lora_f32(model).drop_on()
+    st.lora_drop = model.lora is not None and model.lora.drop_on(model.training)
     if st.lora_drop:
         ops.rng_advance(model.lora.rng)        # new masks for this micro-step, as the bf16 step draws them (TasuModel.forward_llm)
     xn, _, _ = prompt_pass_fp32(model, st, keep=keep)
@@ -253,12 +252,6 @@ class LoraF32:
         self.version = lp.version
         return self.w
 
-    def drop_on(self):
-        return bool(self.m.training and self.lp.cfg.lora_dropout > 0.0)
-
-    def _sid(self, l, t):
-        return l * 8 + TARGETS.index(t)
-
     def _us(self, t, M):
         """[L, M, rk] rank activations of target t, kept for the backward; the pad columns [r, rk) are zero."""
         m, name = self.m, "f32t_lora_us_" + t
@@ -272,7 +265,7 @@ class LoraF32:
         if not drop:
             return x
         xd = self.m._buf("f32t_lora_xd", (M, width), torch.float32)
-        self.m.ops.f32_lora_dropout(x, xd, M, width, self.lp.cfg.lora_dropout, self.lp.rng, self._sid(l, t))
+        self.m.ops.f32_lora_dropout(x, xd, M, width, self.lp.cfg.lora_dropout, self.lp.rng, self.lp.sid(l, t))
         return xd
 
     def forward(self, l, gname, x, y, M, ws, drop):
@@ -307,7 +300,7 @@ class LoraF32:
             if drop:                                                                           # dx += mask . (v A)
                 tmp = m._buf("f32t_lora_tmp", (M, i), f32)
                 ops.f32_gemm(v, w["At"], tmp, M, i, rk, ws=ws)
-                ops.f32_lora_dropout(tmp, dx_base, M, i, p, lp.rng, self._sid(l, t), accumulate=True)
+                ops.f32_lora_dropout(tmp, dx_base, M, i, p, lp.rng, lp.sid(l, t), accumulate=True)
             else:
                 ops.f32_gemm(v, w["At"], dx_base, M, i, rk, resid=dx_base, ws=ws)
             ops.f32_transpose(self._us(t, M)[l], r_t, M, rk, Mp)
@@ -334,7 +327,7 @@ def lora_layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, co
     D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
     f, w = llm.f32["layers"][l], llm.layers[l]
     lo = lora_f32(model)
-    drop = lo.drop_on()
+    drop = lo.lp.drop_on(model.training)
     LDQ = (H + 2 * G) * HD
     ops.f32_gemm(xn, f["wqkv"], qkv, rows, LDQ, D, bias=f["bqkv"], ws=ws)
     lo.forward(l, "qkv", xn, qkv, rows, ws, drop)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 23
+#define TASU_ABI_VERSION 24
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -610,6 +610,26 @@ int tasu_beam_hist_update(int32_t* hist, int32_t* hist_len, const int32_t* ctl, 
 int tasu_logprob_topk_hist(const void* logits, int ld, int M, int V, int k, const int32_t* banned, int n_banned, const int32_t* hist,
                            int hist_ld, const int32_t* hist_len, float penalty, int mode, float* out_val, int32_t* out_idx,
                            float* workspace, int64_t workspace_floats, void* stream);
+/* generate(do_sample = True, num_beams = 1): sampling on the device decode loop (csrc/sample.hip, whose header states the
+ * distribution -- HF's repetition penalty, EOS ban, temperature, top-k with ties kept, top-p -- and the draw).
+ * tasu_sample_uniform: u[r] = float(mix64((seed[0] ^ uint64(counter[0]) * 0x9E3779B97F4A7C15) + uint64(r) * 0xD1B54A32D192ED03) >> 40)
+ * * 2^-24 for r < M, mix64 the splitmix64 finaliser; seed (one int64) and counter (the beam state's ctl: [0] = positions generated)
+ * are DEVICE words, so a replayed graph draws new numbers at every position and in every call.  M <= 256. */
+#define TASU_SAMPLE_POOL 1024
+int tasu_sample_uniform(const int64_t* seed, const int32_t* counter, int M, float* u, void* stream);
+/* One token per row of bf16 logits [M, ld] by inverse CDF in ascending token-id order with the row's uniform u[m] (device, [0, 1)):
+ * banned / hist / hist_ld / hist_len / penalty as in tasu_logprob_topk_hist's mode 1 (hist NULL: no penalty, penalty must be 1);
+ * temperature > 0; 1 <= top_k <= TASU_SAMPLE_POOL (ties at the k-th value are kept, up to the pool's size, then cut by token id);
+ * top_p >= 0 (>= 1: off).  out_val / out_idx [M, 2] in tasu_logprob_topk's format: slot 0 = the token and its log-probability under
+ * the final distribution, slot 1 = (-inf, 0x7fffffff), which tasu_beam_update with one beam never picks.  No floating-point
+ * atomics: bit-identical run to run.  V <= 196608, M <= 256, ld % 8 == 0, rows 16-byte aligned; else TASU_ERR_ARG. */
+int tasu_sample_rows(const void* logits, int ld, int M, int V, const float* u, const int32_t* banned, int n_banned, const int32_t* hist,
+                     int hist_ld, const int32_t* hist_len, float penalty, float temperature, int top_k, float top_p, float* out_val,
+                     int32_t* out_idx, void* stream);
+/* tasu_sample_rows on fp32 logits (ld % 4 == 0). */
+int tasu_f32_sample_rows(const float* logits, int ld, int M, int V, const float* u, const int32_t* banned, int n_banned,
+                         const int32_t* hist, int hist_ld, const int32_t* hist_len, float penalty, float temperature, int top_k,
+                         float top_p, float* out_val, int32_t* out_idx, void* stream);
 /* x[m,:] = table[ids[m],:] (fp32 embedding rows of the last generated tokens). */
 int tasu_embed_rows(const float* table, const int32_t* ids, float* x, int M, int D, void* stream);
 

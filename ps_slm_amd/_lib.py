@@ -111,6 +111,10 @@ PROTOTYPES = {
     "tasu_beam_update": [vp] * 21 + [i32] * 7 + [vp],
     "tasu_beam_hist_update": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "tasu_logprob_topk_hist": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, i64, vp],
+    # generate(do_sample=True, num_beams=1) (csrc/sample.hip)
+    "tasu_sample_uniform": [vp, vp, i32, vp, vp],
+    "tasu_sample_rows": [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp],
+    "tasu_f32_sample_rows": [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp],
     "tasu_fbank": [vp, i64, f32, i32, i32, vp, vp, i32, f32, vp, vp],
     "tasu_lfr_cmvn": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "tasu_embed_rows": [vp, vp, vp, i32, i32, vp],
@@ -182,7 +186,7 @@ PROTOTYPES.update({
     "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm_dispatch.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

@@ -21,6 +21,7 @@ from .model import HD, StepState, rup
 
 NEG = -1.0e9
 BEAM_MAX_NB, BEAM_MAX_B, DECODE_MAX_CTX = 16, 256, 2048   # limits of tasu_beam_update (beams, utterances) / tasu_attn_decode
+SAMPLE_POOL = 1024                                        # TASU_SAMPLE_POOL (include/tasu_hip.h): candidates tasu_sample_rows holds per row
 log = logging.getLogger(__name__)
 _warned_prompt_not_penalised = False
 
@@ -30,6 +31,23 @@ def check_repetition_penalty(penalty):
     if not isinstance(penalty, float) or not penalty > 0:
         raise ValueError(f"`repetition_penalty` must be a strictly positive float, but is {penalty!r}")
     return penalty
+
+
+Sampling = collections.namedtuple("Sampling", "temperature top_k top_p")   # generate(do_sample=True, num_beams=1): the warpers' knobs
+
+
+def check_sampling(temperature=1.0, top_k=50, top_p=1.0):
+    """The checks HF's TemperatureLogitsWarper, TopKLogitsWarper and TopPLogitsWarper make on their arguments -> Sampling.  HF builds
+    the top-p warper only for top_p < 1.0, so a larger value is accepted and turns the step off; ``top_k == 0`` is HF's "no top-k"
+    and passes here (generate_args refuses it: whole-vocabulary sampling is not built)."""
+    if not isinstance(temperature, float) or not temperature > 0:
+        raise ValueError(f"`temperature` (={temperature!r}) must be a strictly positive float")
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or top_k < 0:
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k!r}")
+    top_p = float(top_p)
+    if not top_p >= 0:
+        raise ValueError(f"`top_p` has to be a float >= 0 (>= 1.0 turns it off), but is {top_p!r}")
+    return Sampling(temperature, top_k, min(top_p, 1.0))
 
 
 def penalty_mode(num_beams):
@@ -108,9 +126,10 @@ class BeamState:
 class DeviceBeam:
     """Device-resident beam-search state + the next step's inputs (the arguments of ``tasu_beam_update``)."""
 
-    def __init__(self, model, B, nb, max_new, eos, length_penalty, min_length, S, valid, repetition_penalty=1.0):
+    def __init__(self, model, B, nb, max_new, eos, length_penalty, min_length, S, valid, repetition_penalty=1.0, sampling=None):
         self.B, self.nb, self.max_new, self.eos, self.min_length, self.S = B, nb, max_new, int(eos), int(min_length), S
         self.penalty = float(repetition_penalty)
+        self.sampling = sampling
         up, buf = model._upload, model._buf
         M = B * nb
         i32 = torch.int32
@@ -133,6 +152,13 @@ class DeviceBeam:
         self.next_ids, self.next_src = buf("in_dec_ids", (M,), i32), buf("in_dec_src", (M,), i32)
         self.next_pos, self.next_slot, self.next_lens = buf("in_dec_pos", (M,), i32), buf("in_dec_slot", (M,), i32), buf("in_dec_lens", (M,), i32)
         self.banned = up("dec_banned", np.array([eos if min_length > 0 else -1], dtype=np.int32))
+        self.seed = self.u = None
+        if sampling is not None:
+            # ONE 64-bit seed per sampled call from torch's default CPU generator (torch.manual_seed makes the call reproducible); it
+            # and the position counter ctl[0] are device words the uniform kernel reads, so a replayed graph draws new numbers
+            seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            self.seed = up("smp_seed", np.array([seed], dtype=np.int64))
+            self.u = buf("smp_u", (M,), torch.float32)
         self.hist = self.hist_len = None
         if self.penalty != 1.0:
             # generated tokens of every beam row (tasu_beam_hist_update keeps them next to the beam state): what HF's
@@ -200,7 +226,8 @@ def check_kv_cache_fits(model, B, nb, ctx, elem_bytes, names):
 
 
 def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention,
-                  repetition_penalty=1.0, kv_elem_bytes=2, kv_names=("dec_kc", "dec_vc")):
+                  repetition_penalty=1.0, kv_elem_bytes=2, kv_names=("dec_kc", "dec_vc"), sampling=None,
+                  sample_ops=("sample_uniform", "sample_rows")):
     """Checks a generate() call against the limits of the device beam search (tasu_beam_update: include/tasu_hip.h), the context
     limit ``max_ctx`` of the caller's cache attention and the device's free memory (the KV caches ``kv_names``), BEFORE any
     prefill.  Returns (min_length in generated positions, eos, pad)."""
@@ -213,6 +240,19 @@ def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_toke
         raise ValueError("max_new_tokens must be >= 1")
     if S + max_new_tokens > max_ctx:
         raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds {attention} context limit {max_ctx}")
+    if sampling is not None:                              # do_sample=True: raised before any prefill work, like the penalty's
+        if nb != 1:
+            raise NotImplementedError(f"generate(do_sample=True, num_beams={nb}): sampling is served at num_beams=1 only (beam-sample is "
+                                      "not built)")
+        if sampling.top_k == 0:
+            raise NotImplementedError("generate(do_sample=True, top_k=0): whole-vocabulary sampling is not built; the sampler keeps the "
+                                      f"top_k best tokens of a row in a pool of {SAMPLE_POOL}, 1 <= top_k <= {SAMPLE_POOL}")
+        if sampling.top_k > SAMPLE_POOL:
+            raise NotImplementedError(f"generate(do_sample=True, top_k={sampling.top_k}): the sampler's candidate pool holds "
+                                      f"{SAMPLE_POOL} tokens per row, 1 <= top_k <= {SAMPLE_POOL}")
+        if not all(hasattr(model.ops, n) for n in sample_ops):
+            raise NotImplementedError(f"generate(do_sample=True): the ops backend {type(model.ops).__name__} has no sampling kernels "
+                                      f"({', '.join(sample_ops)})")
     if check_repetition_penalty(repetition_penalty) != 1.0:
         if not hasattr(model.ops, "beam_hist_update"):   # a missing kernel is an error, raised before any prefill work
             raise NotImplementedError(f"generate(repetition_penalty={repetition_penalty!r}): the ops backend {type(model.ops).__name__} "
@@ -254,6 +294,8 @@ def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
         key = (tag, bs.B, bs.S, bs.nb, bs.S + bs.max_new, bs.max_new, bs.eos, bs.min_length)
         if bs.penalty != 1.0:
             key += (bs.penalty,)
+        if bs.sampling is not None:                        # (not the seed: the kernels read it from device memory)
+            key += ("sample",) + tuple(bs.sampling)
         step = lambda: model._dec_graphs.run(key, device_step, lambda: model._buf_gen)
     if model.device.type == "cuda":
         # the host issues positions ahead of the device and looks at the pinned "done" word DONE_POLL_DEPTH positions late
@@ -276,8 +318,9 @@ def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
 
 
 def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
-                         eos_token_id=None, pad_token_id=None, repetition_penalty=1.0):
-    """st: a prepared state whose projector output (st.dev['y2']) is ready.  Returns LongTensor [B, n_new] (CPU)."""
+                         eos_token_id=None, pad_token_id=None, repetition_penalty=1.0, sampling=None):
+    """st: a prepared state whose projector output (st.dev['y2']) is ready.  ``sampling``: a Sampling (check_sampling) for
+    generate(do_sample=True, num_beams=1), None for beam search / greedy.  Returns LongTensor [B, n_new] (CPU)."""
     if model.lora is not None and model._lora_run is not None:
         # use_peft: prefill and the decode loop run on the merged weights W + s B A (ps_slm_amd/lora.py: merged_llm)
         from .lora import merged_llm
@@ -285,12 +328,12 @@ def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, 
         model.llm, model._lora_run = merged_llm(model), None
         try:
             return beam_search_generate(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos_token_id, pad_token_id,
-                                        repetition_penalty)
+                                        repetition_penalty, sampling)
         finally:
             model.llm, model._lora_run = keep
     ops, geo = model.ops, model.geo
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, DECODE_MAX_CTX,
-                                         "the cache attention's", repetition_penalty)
+                                         "the cache attention's", repetition_penalty, sampling=sampling)
     # ---- prefill with the training-forward kernels (no loss)
     model.forward_llm(st, compute_loss=False, need_backward=False, logits_rows="none")
     # decode-step weights in the order the streaming kernels consume them (built once per model), and the decision whether the
@@ -298,7 +341,8 @@ def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, 
     model.llm.prepare_decode(ops)
     ops.begin_decode(geo.llm_dim, geo.llm_heads * HD, geo.llm_inter)
     try:
-        return _decode_after_prefill(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty)
+        return _decode_after_prefill(model, st, num_beams, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty,
+                                     sampling)
     finally:
         ops.end_decode()
 
@@ -349,7 +393,7 @@ def layers_per_gemm(ops, geo, layers, final_norm, x, x2, xn, qkv, ao, act, cos, 
                 in_ssq[ci] = None
 
 
-def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty=1.0):
+def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_penalty, eos, pad, repetition_penalty=1.0, sampling=None):
     ops, geo, llm = model.ops, model.geo, model.llm
     B, S = st.B, st.S
     M, K = B * nb, 2 * nb
@@ -377,13 +421,19 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     ops.gemm(xn, llm.head, logits, B, V, D)
     tv = buf("dec_topv", (M, K), f32)
     ti = buf("dec_topi", (M, K), i32)
-    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty)
+    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty, sampling)
     penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
 
     def topk_and_update(rows, first):
         """Per-row top-k and the beam update; under a repetition penalty the top-k reads every row's token history and the
-        history follows the beams after the update (``repetition_penalty == 1.0``: exactly the launches without the knob)."""
-        if penalised:
+        history follows the beams after the update (``repetition_penalty == 1.0``: exactly the launches without the knob).
+        do_sample: the position's uniforms and one sampled token per row take the top-k's place (``do_sample=False``: exactly the
+        launches without the knob)."""
+        if sampling is not None:
+            ops.sample_uniform(bs.seed, bs.ctl, rows, bs.u)
+            ops.sample_rows(logits, rows, V, bs.u, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, sampling.temperature, sampling.top_k,
+                            sampling.top_p, tv, ti)
+        elif penalised:
             ops.logprob_topk_hist(logits, rows, V, K, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, pmode, tv, ti)
         else:
             ops.logprob_topk(logits, rows, V, K, bs.banned, 1, tv, ti)

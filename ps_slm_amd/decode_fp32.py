@@ -241,12 +241,14 @@ def forward_fp32(model, st: StepState, compute_loss=True):
 
 
 def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
-                              eos_token_id=None, pad_token_id=None, repetition_penalty=1.0):
-    """st: a prepared state (prepare_text / prepare_audio).  Returns LongTensor [B, n_new] (CPU)."""
+                              eos_token_id=None, pad_token_id=None, repetition_penalty=1.0, sampling=None):
+    """st: a prepared state (prepare_text / prepare_audio); ``sampling`` as in decode.beam_search_generate.  Returns LongTensor
+    [B, n_new] (CPU)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, F32_MAX_CTX,
-                                         "the fp32 attention's", repetition_penalty, kv_elem_bytes=4, kv_names=("f32_kc", "f32_vc"))
+                                         "the fp32 attention's", repetition_penalty, kv_elem_bytes=4, kv_names=("f32_kc", "f32_vc"),
+                                         sampling=sampling, sample_ops=("sample_uniform", "f32_sample_rows"))
     B, S, nb = st.B, st.S, num_beams
     ctx = S + max_new_tokens
     M, K = B * nb, 2 * nb
@@ -273,13 +275,17 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     ops.embed_rows(xn0, last_rows, xn, B, D)                    # the final-normed last prompt position of every utterance
     ops.f32_gemm(xn, weights_f32(model)["head"], logits, B, V, D, ws=ws)
     tv, ti = buf("dec_topv", (M, K), f32), buf("dec_topi", (M, K), i32)
-    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty)
+    bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty, sampling)
     topk_ws = buf("f32_topk_ws", (M * 16 * (2 + 2 * K),), f32)               # the row split over 16 workgroups (tasu_f32_logprob_topk)
     penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
 
     def topk_and_update(rows, first):
         """decode.py's topk_and_update on the fp32 logits (``repetition_penalty == 1.0``: exactly the launches without the knob)."""
-        if penalised:
+        if sampling is not None:
+            ops.sample_uniform(bs.seed, bs.ctl, rows, bs.u)
+            ops.f32_sample_rows(logits, rows, V, bs.u, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, sampling.temperature, sampling.top_k,
+                                sampling.top_p, tv, ti)
+        elif penalised:
             ops.f32_logprob_topk_hist(logits, rows, V, K, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, pmode, tv, ti, ws=topk_ws)
         else:
             ops.f32_logprob_topk(logits, rows, V, K, bs.banned, 1, tv, ti, ws=topk_ws)

@@ -749,6 +749,25 @@ class HipOps:
                                                   _p(hist_len), float(penalty), int(mode), _p(out_val), _p(out_idx), _p(self.topk_ws),
                                                   self.topk_ws.numel(), self._stream()), "tasu_logprob_topk_hist")
 
+    def sample_uniform(self, seed, counter, M, u):
+        """u[:M] = the uniforms of generated position counter[0] under the call's seed (tasu_sample_uniform; both device words)."""
+        self._chk(self.lib.tasu_sample_uniform(_p(seed), _p(counter), M, _p(u), self._stream()), "tasu_sample_uniform")
+
+    def _sample_rows(self, fn, name, logits, M, V, u, banned, n_banned, hist, hist_len, penalty, temperature, top_k, top_p, out_val, out_idx):
+        self._chk(fn(_p(logits), logits.stride(0), M, V, _p(u), _p(banned), n_banned, _p(hist), hist.stride(0) if hist is not None else 0,
+                     _p(hist_len), float(penalty), float(temperature), int(top_k), float(top_p), _p(out_val), _p(out_idx), self._stream()), name)
+
+    def sample_rows(self, logits, M, V, u, banned, n_banned, hist, hist_len, penalty, temperature, top_k, top_p, out_val, out_idx):
+        """One sampled token per row of bf16 logits, ``out_val`` / ``out_idx`` [M, 2] in logprob_topk's format (tasu_sample_rows;
+        ``hist`` None: no repetition penalty)."""
+        self._sample_rows(self.lib.tasu_sample_rows, "tasu_sample_rows", logits, M, V, u, banned, n_banned, hist, hist_len, penalty,
+                          temperature, top_k, top_p, out_val, out_idx)
+
+    def f32_sample_rows(self, logits, M, V, u, banned, n_banned, hist, hist_len, penalty, temperature, top_k, top_p, out_val, out_idx):
+        """sample_rows on fp32 logits (tasu_f32_sample_rows)."""
+        self._sample_rows(self.lib.tasu_f32_sample_rows, "tasu_f32_sample_rows", logits, M, V, u, banned, n_banned, hist, hist_len, penalty,
+                          temperature, top_k, top_p, out_val, out_idx)
+
     def beam_hist_update(self, bs):
         """Every beam row's token history after beam_update (tasu_beam_hist_update); ``bs``: ps_slm_amd.decode.DeviceBeam."""
         self._chk(self.lib.tasu_beam_hist_update(_p(bs.hist), _p(bs.hist_len), _p(bs.ctl), _p(bs.next_src), _p(bs.next_ids), bs.B, bs.nb,

@@ -347,6 +347,19 @@ def model_factory(train_config, model_config, **kwargs):
     return model, tokenizer
 
 
+def default_top_k(model_config):
+    """generate(do_sample=True) without ``top_k``: the reference never passes one, so HF takes it from the model's generation config
+    -- ``top_k`` of <llm_path>/generation_config.json when that file has one, otherwise GenerationConfig's default 50."""
+    path = os.path.join(str(model_config.get("llm_path", "") or ""), "generation_config.json")
+    if os.path.isfile(path):
+        import json
+        with open(path) as f:
+            top_k = json.load(f).get("top_k")
+        if top_k is not None:
+            return top_k
+    return 50
+
+
 # ------------------------------------------------------------------------------------------------ the model
 NO_GRAPH_MSG = ("ps_slm_amd: this loss was computed in eval mode (model.eval() / need_backward=False): the step kept no activations "
                 "for a backward pass.  Call model.train() before the forward whose loss you want to differentiate")
@@ -635,15 +648,23 @@ class slam_model_asr:
         from ps_slm_amd.decode import beam_search_generate
         core = self.core
         self._refresh_if_touched()
-        # the decode loop is HF beam search with do_sample=False (ps-slm.py:660-675 defaults): a sampling knob set to anything else
-        # would silently be ignored, so it is rejected; repetition_penalty is served (ps_slm_amd/decode.py, HF's processor)
-        from ps_slm_amd.decode import check_repetition_penalty
+        # the decode loop is HF beam search / greedy with do_sample=False (ps-slm.py:660-675 defaults) or HF sampling at num_beams=1
+        # (do_sample=True: csrc/sample.hip); repetition_penalty is served on all of them (ps_slm_amd/decode.py, HF's processor).  A
+        # sampling knob HF would silently ignore (no do_sample) and beam-sample (do_sample with num_beams > 1) are rejected
+        from ps_slm_amd.decode import check_repetition_penalty, check_sampling
         repetition_penalty = check_repetition_penalty(kwargs.get("repetition_penalty", 1.0))
-        for name, default in (("do_sample", False), ("top_p", 1.0), ("temperature", 1.0)):
-            if kwargs.get(name, default) != default:
-                raise NotImplementedError(f"generate({name}={kwargs[name]!r}): the MI355X decode loop implements the reference's "
-                                          f"defaults only ({name}={default!r}, Multitask/model/ps-slm.py:660-675: beam search "
-                                          "without sampling or temperature)")
+        num_beams = kwargs.get("num_beams", 4)
+        sampling = None
+        if kwargs.get("do_sample", False) is True and num_beams == 1:
+            sampling = check_sampling(kwargs.get("temperature", 1.0), kwargs.get("top_k", default_top_k(self.model_config)),
+                                      kwargs.get("top_p", 1.0))
+        else:
+            for name, default in (("do_sample", False), ("top_p", 1.0), ("temperature", 1.0), ("top_k", None)):
+                if kwargs.get(name, default) != default:
+                    raise NotImplementedError(f"generate({name}={kwargs[name]!r}, num_beams={num_beams!r}): the MI355X decode loop serves "
+                                              "the sampling knobs as do_sample=True with num_beams=1 only (Multitask/model/ps-slm.py:"
+                                              f"660-675); {name} without do_sample=True would silently be ignored, and beam-sample "
+                                              "(do_sample=True with num_beams > 1) is not built")
         if self.gt_emb:                                     # ps-slm.py:590-598
             texts = [re.sub(r"[^A-Za-z\s.,!?]+", "", t).lower().strip() for t in targets]
             ids_list = [self.encoder_tokenizer.encode(t) for t in texts]
@@ -655,7 +676,7 @@ class slam_model_asr:
                                     do_psd=self.do_psd)
         if core.arith == "fp32":                           # use_fp16 = false: the reference's own decode arithmetic
             from ps_slm_amd.decode_fp32 import beam_search_generate_fp32 as beam_search_generate
-        return beam_search_generate(core, st, num_beams=kwargs.get("num_beams", 4),
+        return beam_search_generate(core, st, num_beams=num_beams, sampling=sampling,
                                     max_new_tokens=kwargs.get("max_new_tokens", 200),
                                     min_length=kwargs.get("min_length", 1),
                                     length_penalty=kwargs.get("length_penalty", 1.0),

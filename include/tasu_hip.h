@@ -630,6 +630,32 @@ int tasu_sample_rows(const void* logits, int ld, int M, int V, const float* u, c
 int tasu_f32_sample_rows(const float* logits, int ld, int M, int V, const float* u, const int32_t* banned, int n_banned,
                          const int32_t* hist, int hist_ld, const int32_t* hist_len, float penalty, float temperature, int top_k,
                          float top_p, float* out_val, int32_t* out_idx, void* stream);
+/* generate(do_sample = True, num_beams = nb > 1): HF's beam-search multinomial sampling on the device decode loop (csrc/sample.hip's
+ * header states the distribution and the draw).  Per output row m = b * nb + j of bf16 logits (first = 1: logits row m / nb, the
+ * prompt's last position): lp = log_softmax(x) in tasu_logprob_topk's form, the repetition penalty on lp (tasu_logprob_topk_hist's
+ * mode 0), the ban, s = lp' / T, top-k at max(top_k, 2), top-p that keeps the two largest; then for every survivor v
+ *   a = s + run_scores[m],  key = a - logf(-logf(u)),  u = (float(mix64((seed[0] ^ uint64(ctl[0]) * 0x9E3779B97F4A7C15) +
+ *   uint64(m * V + v) * 0xD1B54A32D192ED03) >> 41) + 0.5) * 2^-23,
+ * and out_key / out_val (= a) / out_idx [M, K] = the row's K largest keys in the order (key desc, v asc), the rest (-inf, -inf,
+ * 0x7fffffff).  seed, ctl, run_scores are DEVICE memory (a replayed graph draws new numbers).  1 <= K <= 32, M % n_beams == 0, the
+ * other limits are tasu_sample_rows'; else TASU_ERR_ARG.  No floating-point atomics. */
+int tasu_beam_sample_rows(const void* logits, int ld, int M, int V, int K, int n_beams, int first, const int64_t* seed, const int32_t* ctl,
+                          const float* run_scores, const int32_t* banned, int n_banned, const int32_t* hist, int hist_ld,
+                          const int32_t* hist_len, float penalty, float temperature, int top_k, float top_p, float* out_key,
+                          float* out_val, int32_t* out_idx, void* stream);
+/* tasu_beam_sample_rows on fp32 logits (ld % 4 == 0), log_softmax in tasu_f32_logprob_topk's form. */
+int tasu_f32_beam_sample_rows(const float* logits, int ld, int M, int V, int K, int n_beams, int first, const int64_t* seed,
+                              const int32_t* ctl, const float* run_scores, const int32_t* banned, int n_banned, const int32_t* hist,
+                              int hist_ld, const int32_t* hist_len, float penalty, float temperature, int top_k, float top_p,
+                              float* out_key, float* out_val, int32_t* out_idx, void* stream);
+/* tasu_beam_update for tasu_beam_sample_rows' output (keys / vals / idx [B * n_beams, 2 n_beams], B * n_beams rows at every
+ * position, the first included): an utterance's 2 n_beams candidates are its largest KEYS in the order (key desc, beam asc, token
+ * asc); the update then runs on (vals, beam, token) in that order exactly as tasu_beam_update's does on its sorted candidates. */
+int tasu_beam_update_drawn(const float* keys, const float* vals, const int32_t* idx, float* run_scores, float* fin_scores,
+                           int32_t* fin_len, int32_t* fin_par, int32_t* fin_tok, int32_t* is_fin, int32_t* unsat, int32_t* bp_tok,
+                           int32_t* bp_par, const float* len_pow, int32_t* ctl, int32_t* done_host, const int32_t* valid,
+                           int32_t* next_ids, int32_t* next_src, int32_t* next_pos, int32_t* next_slot, int32_t* next_lens,
+                           int32_t* banned, int B, int n_beams, int max_new, int eos, int min_length, int S, void* stream);
 /* x[m,:] = table[ids[m],:] (fp32 embedding rows of the last generated tokens). */
 int tasu_embed_rows(const float* table, const int32_t* ids, float* x, int M, int D, void* stream);
 

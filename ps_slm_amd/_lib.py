@@ -115,6 +115,10 @@ PROTOTYPES = {
     "tasu_sample_uniform": [vp, vp, i32, vp, vp],
     "tasu_sample_rows": [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp],
     "tasu_f32_sample_rows": [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp],
+    # generate(do_sample=True, num_beams>1): beam-sample (csrc/sample.hip, csrc/beam.hip)
+    "tasu_beam_sample_rows": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp, vp],
+    "tasu_f32_beam_sample_rows": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, f32, f32, i32, f32, vp, vp, vp, vp],
+    "tasu_beam_update_drawn": [vp] * 22 + [i32] * 6 + [vp],
     "tasu_fbank": [vp, i64, f32, i32, i32, vp, vp, i32, f32, vp, vp],
     "tasu_lfr_cmvn": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "tasu_embed_rows": [vp, vp, vp, i32, i32, vp],

@@ -15,6 +15,13 @@
 // reorder, position ids, cache slots, lengths, the EOS ban while cur < min_length), so the whole decode step replays as one
 // hipGraph with no host round trip; ctl[0] = positions generated so far, ctl[1] = done (then the kernels are no-ops).
 //
+// tasu_beam_update_drawn is the same position under generate(do_sample = True, num_beams > 1), HF's beam-search multinomial sampling:
+// the rows' K candidates come from tasu_beam_sample_rows (csrc/sample.hip, whose header states the distribution and the draw) with a
+// Gumbel key each, the utterance's K are the K LARGEST KEYS in the order (key desc, beam asc, token asc) -- the draw order of sampling
+// without replacement in proportion to softmax(accumulated score) -- and everything after that runs on (accumulated score, beam,
+// token) in that order, as HF does with the unsorted output of torch.multinomial: the running beams are the best nb non-stopped BY
+// SCORE (ties: the earlier slot), and only the first nb slots of the draw may enter the finished heap.
+//
 // Up to BEAM_MAX_NB beams an utterance's nb * K candidates fit one wave (beam_update_kernel, one launch); up to BEAM_WIDE_MAX_NB
 // they take a workgroup (beam_update_wide_kernel + beam_finish_kernel).  The two differ in how the K best are found; what follows
 // -- the running set, the finished-hypothesis merge and the unsat test -- is beam_select, one wave's work in both.
@@ -49,11 +56,25 @@ struct BeamArgs {
   int32_t* next_lens;
   int32_t* banned;            // [1]: eos while the next position is still below min_length, else -1
   int B, nb, max_new, eos, min_length, S, first;
+  const float* keys;          // DRAWN: [B * nb, K] the candidates' Gumbel keys (vals then hold ACCUMULATED scores, B * nb rows always)
 };
 
 // candidate c = (beam c / K, k-th best of that beam): its score and token
-__device__ __forceinline__ void beam_candidate(const BeamArgs& p, int b, int c, int K, float& cs, int& ct) {
+// DRAWN (beam-sample, tasu_beam_update_drawn): the candidate's accumulated score and token as tasu_beam_sample_rows wrote them, and
+// its key ck, by which the K best are chosen; a filler (0x7fffffff) becomes token 0 at -inf, inside the embedding table.  Otherwise ck
+// is the score itself.
+template <bool DRAWN>
+__device__ __forceinline__ void beam_candidate(const BeamArgs& p, int b, int c, int K, float& cs, int& ct, float& ck) {
   const int j = c / K, k = c - j * K;
+  if constexpr (DRAWN) {
+    const size_t o = ((size_t)b * p.nb + j) * K + k;
+    ct = p.idx[o];
+    const bool real = ct >= 0 && ct != 0x7fffffff;
+    cs = real ? p.vals[o] : -__builtin_inff();
+    ck = real ? p.keys[o] : -__builtin_inff();
+    if (!real) ct = 0;
+    return;
+  }
   float v = BEAM_NEG;
   ct = 0;
   if (!p.first || j == 0) {
@@ -62,6 +83,7 @@ __device__ __forceinline__ void beam_candidate(const BeamArgs& p, int b, int c, 
     ct = p.idx[row * K + k];
   }
   cs = v + p.run_scores[b * p.nb + j];
+  ck = cs;
 }
 // candidate (sd, td) at index d of beam jd precedes candidate (cs, ct) at index c of beam j
 __device__ __forceinline__ bool beam_before(float sd, int jd, int td, int d, float cs, int j, int ct, int c) {
@@ -167,6 +189,7 @@ __device__ __forceinline__ void beam_close_position(const BeamArgs& p, int cur, 
 // nb <= BEAM_MAX_NB.  One WAVE per utterance (16 utterances per pass of a 1024-thread block): lane c < nb * K holds candidate c and
 // ranks it against the others with wave shuffles (the first, thread-per-utterance form of this kernel spent 88 us per position in
 // scratch-memory loops).
+template <bool DRAWN>
 __global__ __launch_bounds__(1024) void beam_update_kernel(BeamArgs p) {
   __shared__ int s_unsat_any, s_stop_all;
   __shared__ float s_top_lp[16][2 * BEAM_MAX_NB];
@@ -183,15 +206,15 @@ __global__ __launch_bounds__(1024) void beam_update_kernel(BeamArgs p) {
   const float lp_now = p.len_pow[cur + 1];
   for (int b = wave; b < p.B; b += 16) {                  // wave-uniform loop
     const int j = lane / K;
-    float cs = -__builtin_inff();
+    float cs = -__builtin_inff(), ck = -__builtin_inff();
     int ct = 0;
-    if (lane < NC) beam_candidate(p, b, lane, K, cs, ct);
-    // ---- top K by (score desc, beam asc, token asc, candidate index asc)
+    if (lane < NC) beam_candidate<DRAWN>(p, b, lane, K, cs, ct, ck);
+    // ---- top K by (score desc, beam asc, token asc, candidate index asc); DRAWN: by key, the draw order
     int rank = 0;
     for (int d = 0; d < NC; ++d) {
-      const float sd = __shfl(cs, d, 64);
+      const float sd = __shfl(ck, d, 64);
       const int td = __shfl(ct, d, 64);
-      rank += beam_before(sd, d / K, td, d, cs, j, ct, lane) ? 1 : 0;
+      rank += beam_before(sd, d / K, td, d, ck, j, ct, lane) ? 1 : 0;
     }
     if (lane < NC && rank < K) {
       s_top_lp[wave][rank] = cs;
@@ -219,6 +242,7 @@ __global__ __launch_bounds__(1024) void beam_update_kernel(BeamArgs p) {
 // bit 0 = the utterance can still improve, bit 1 = one of its K best does not stop -- and beam_finish_kernel (one block, the next
 // launch on the stream) reduces them, puts unsat[b] back to 0 / 1 and closes the position: no workgroup waits for another, the value
 // cannot depend on the order in which they finish, and the state is the call's own (two decodes on two streams do not meet).
+template <bool DRAWN>
 __global__ __launch_bounds__(BEAM_WIDE_THREADS) void beam_update_wide_kernel(BeamArgs p) {
   __shared__ float s_cs[BEAM_WIDE_THREADS];
   __shared__ int s_ct[BEAM_WIDE_THREADS];
@@ -230,10 +254,10 @@ __global__ __launch_bounds__(BEAM_WIDE_THREADS) void beam_update_wide_kernel(Bea
   if (p.ctl[1]) return;                                   // finished earlier: leave every output as it is (block-uniform)
   const float lp_now = p.len_pow[cur + 1];
   const int j = t / K;
-  float cs = -__builtin_inff();
+  float cs = -__builtin_inff(), ck = -__builtin_inff();
   int ct = 0;
-  if (t < NC) beam_candidate(p, b, t, K, cs, ct);
-  s_cs[t] = cs;
+  if (t < NC) beam_candidate<DRAWN>(p, b, t, K, cs, ct, ck);
+  s_cs[t] = ck;                                           // (what the candidates are ranked by; DRAWN: the key)
   s_ct[t] = ct;
   __syncthreads();
   // ---- top K by (score desc, beam asc, token asc, candidate index asc)
@@ -241,7 +265,7 @@ __global__ __launch_bounds__(BEAM_WIDE_THREADS) void beam_update_wide_kernel(Bea
     int rank = 0;
     for (int d0 = 0; d0 < NC; d0 += K) {                  // beam jd = d0 / K
       const int jd = d0 / K;
-      for (int d = d0; d < d0 + K; ++d) rank += beam_before(s_cs[d], jd, s_ct[d], d, cs, j, ct, t) ? 1 : 0;
+      for (int d = d0; d < d0 + K; ++d) rank += beam_before(s_cs[d], jd, s_ct[d], d, ck, j, ct, t) ? 1 : 0;
     }
     if (rank < K) {
       s_top_lp[rank] = cs;
@@ -324,11 +348,33 @@ extern "C" int tasu_beam_update(const float* vals, const int32_t* idx, float* ru
              done_host, valid, next_ids, next_src, next_pos, next_slot, next_lens, banned, B, n_beams, max_new, eos,
              min_length, S, first};
   if (n_beams > BEAM_MAX_NB) {                            // a workgroup per utterance, then the batch-wide done flag
-    TASU_LAUNCH(beam_update_wide_kernel, dim3(B), dim3(BEAM_WIDE_THREADS), 0, (hipStream_t)stream, a);
+    TASU_LAUNCH(beam_update_wide_kernel<false>, dim3(B), dim3(BEAM_WIDE_THREADS), 0, (hipStream_t)stream, a);
     TASU_LAUNCH(beam_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     return TASU_OK;
   }
-  TASU_LAUNCH(beam_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  TASU_LAUNCH(beam_update_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  return TASU_OK;
+}
+
+extern "C" int tasu_beam_update_drawn(const float* keys, const float* vals, const int32_t* idx, float* run_scores, float* fin_scores,
+                                      int32_t* fin_len, int32_t* fin_par, int32_t* fin_tok, int32_t* is_fin, int32_t* unsat,
+                                      int32_t* bp_tok, int32_t* bp_par, const float* len_pow, int32_t* ctl, int32_t* done_host,
+                                      const int32_t* valid, int32_t* next_ids, int32_t* next_src, int32_t* next_pos, int32_t* next_slot,
+                                      int32_t* next_lens, int32_t* banned, int B, int n_beams, int max_new, int eos, int min_length, int S,
+                                      void* stream) {
+  if (!keys || !vals || !idx || !run_scores || !fin_scores || !fin_len || !fin_par || !fin_tok || !is_fin || !unsat || !bp_tok ||
+      !bp_par || !len_pow || !ctl || !valid || !next_ids || !next_src || !next_pos || !next_slot || !next_lens || !banned)
+    return TASU_ERR_ARG;
+  if (B <= 0 || B > 256 || n_beams <= 0 || n_beams > BEAM_WIDE_MAX_NB || max_new <= 0 || S <= 0) return TASU_ERR_ARG;
+  BeamArgs a{vals, idx, run_scores, fin_scores, fin_len, fin_par, fin_tok, is_fin, unsat, bp_tok, bp_par, len_pow, ctl,
+             done_host, valid, next_ids, next_src, next_pos, next_slot, next_lens, banned, B, n_beams, max_new, eos,
+             min_length, S, 0, keys};
+  if (n_beams > BEAM_MAX_NB) {
+    TASU_LAUNCH(beam_update_wide_kernel<true>, dim3(B), dim3(BEAM_WIDE_THREADS), 0, (hipStream_t)stream, a);
+    TASU_LAUNCH(beam_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return TASU_OK;
+  }
+  TASU_LAUNCH(beam_update_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
   return TASU_OK;
 }
 

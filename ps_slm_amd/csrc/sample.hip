@@ -44,6 +44,27 @@
 // distribution, slot 1 = (-inf, 0x7fffffff).  With one beam, tasu_beam_update ranks slot 1 behind slot 0 whatever slot 0 holds
 // (-inf + anything < a finite score, and EOS's -1e9 keeps slot 0 finite), so the filler never becomes the running token.
 // A row without a selectable column (all -inf / NaN) yields token 0 with -inf: ids stay inside the embedding table.
+//
+// generate(do_sample = True, num_beams = nb > 1), HF's beam-search multinomial sampling (_beam_search with do_sample): tasu_beam_sample_rows
+// / tasu_f32_beam_sample_rows, the same kernel with BEAM set; tasu_beam_update_drawn (csrc/beam.hip) consumes its output.
+// THE DISTRIBUTION is HF's, per beam row, on fp32 values:
+//   0. lp = log_softmax(x) over all V columns, in tasu_logprob_topk's form of the arithmetic mode: bf16 logits x - (max + __logf(sum
+//      __expf(x - max))), fp32 logits (x - max) - logf(sum expf(x - max)); the sum is a fixed tree
+//   1. repetition penalty ON THE LOG-PROBS of the row's history tokens (mode 0 of csrc/topk.hip), once per distinct token, no renormalisation
+//   2. the EOS ban;   3. s = lp' / T, a true division
+//   4. top-k at max(top_k, 2) and 5. top-p that never removes the two largest: with more than one beam HF builds the warpers with
+//      min_tokens_to_keep = 2.  Ties, the pool's id cut and the ascending-mass form are those of one beam.  Nothing is renormalised.
+//   6. HF draws 2 nb of an utterance's nb * V accumulated scores a = s + running score WITHOUT REPLACEMENT in proportion to softmax(a).
+// THE DRAW is ours: the Plackett-Luce order of softmax(a) by Gumbel keys, which needs no serial walk per utterance and cannot run out
+// of mass.  For output row m = b * nb + j, surviving column v, generated position t (ctl[0]) and the call's seed (both device words):
+//   z   = mix64((seed ^ uint64(t) * 0x9E3779B97F4A7C15) + uint64(m * V + v) * 0xD1B54A32D192ED03)
+//   u   = (float(z >> 41) + 0.5) * 2^-23                     (23 bits and a half: exact in fp32, 0 < u < 1)
+//   key = fl(a + G),  G = -logf(-logf(u)),  a = fl(s + run_scores[m])
+// The utterance's draw order is its 2 nb largest keys, descending, then (beam, column) ascending; a row hands over its own K = 2 nb
+// largest as out_key / out_val (= a) / out_idx [M, K] in that order, the rest (-inf, -inf, 0x7fffffff).  A filtered column is never a
+// candidate: where torch.multinomial would fill a draw of more entries than have probability from zero-probability categories in an
+// unspecified order, the keys decide (at the first position beams >= 1, at -1e9, supply them).  `first`: output row m reads logits
+// row m / nb (the prompt's last position, B rows of logits).
 #include "common.h"
 #include "../../include/tasu_hip.h"
 
@@ -159,15 +180,25 @@ struct SampleVec<float> {
   static constexpr int VEC = 4;
 };
 
-template <typename T, bool HIST>
+// what the BEAM form of sample_rows_kernel needs on top: the device words of the RNG, the rows' running scores, the output
+struct BeamDraw {
+  const int64_t* seed;
+  const int32_t* ctl;
+  const float* run_scores;    // [M]
+  float* out_key;             // [M, K]
+  int nb, first, K;
+};
+
+template <typename T, bool HIST, bool BEAM>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __restrict__ logits, int ld, int V,
                                                                      const float* __restrict__ u, const int32_t* __restrict__ banned,
                                                                      int n_banned, const int32_t* __restrict__ hist, int hist_ld,
                                                                      const int32_t* __restrict__ hist_len, float penalty, float temp,
                                                                      int top_k, float top_p, float* __restrict__ out_val,
-                                                                     int32_t* __restrict__ out_idx) {
+                                                                     int32_t* __restrict__ out_idx, BeamDraw bd) {
   typedef typename SampleVec<T>::type VT;
   constexpr int VEC = SampleVec<T>::VEC;
+  constexpr bool FAST = sizeof(T) == 2;                            // (BEAM) bf16 logits: tasu_logprob_topk's __expf / __logf form
   __shared__ int bins[SAMPLE_BINS];
   __shared__ int wt_i[SAMPLE_WAVES];
   __shared__ float wt_f[SAMPLE_WAVES];
@@ -178,7 +209,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
   __shared__ float s_stat[2];
   __shared__ unsigned hbits[HIST ? SAMPLE_MAX_V / 32 : 1];
   const int row = blockIdx.x, t = threadIdx.x;
-  const T* x = logits + (size_t)row * ld;
+  const T* x = logits + (size_t)(BEAM && bd.first ? row / bd.nb : row) * ld;
   const int nchunk = (V + VEC - 1) / VEC;                          // (ld % VEC == 0 and ld >= V: the last chunk lies inside the row)
   if constexpr (HIST) {
     const int nword = (V + 31) / 32;
@@ -193,6 +224,38 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
   }
   if (t == 0) s_count = 0, s_surv = 0;
   __syncthreads();
+  // step 0 (BEAM): the row's max and log-sum-exp over all V columns
+  float lse_mx = 0.f, lse_lg = 0.f;
+  if constexpr (BEAM) {
+    float m = -__builtin_inff();
+    for (int c = t; c < nchunk; c += SAMPLE_THREADS) {
+      const VT xs = *(const VT*)(x + (size_t)c * VEC);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        if (c * VEC + j < V) m = fmaxf(m, (float)xs[j]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((t & 63) == 0) wt_f[t >> 6] = m;
+    __syncthreads();
+    m = wt_f[0];
+    for (int i = 1; i < SAMPLE_WAVES; ++i) m = fmaxf(m, wt_f[i]);
+    float sum = 0.f;
+    for (int c = t; c < nchunk; c += SAMPLE_THREADS) {
+      const VT xs = *(const VT*)(x + (size_t)c * VEC);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float v = (float)xs[j];
+        if (c * VEC + j < V && v > -__builtin_inff()) sum += FAST ? __expf(v - m) : expf(v - m);
+      }
+    }
+    const float tot = block_scan<float, false>(sum, wt_f);         // (a fixed tree; the last thread holds the row's sum)
+    if (t == SAMPLE_THREADS - 1) s_stat[0] = tot;
+    __syncthreads();
+    lse_mx = m;
+    lse_lg = FAST ? __logf(s_stat[0]) : logf(s_stat[0]);
+    __syncthreads();
+  }
   const int ban0 = n_banned > 0 ? banned[0] : -1, ban1 = n_banned > 1 ? banned[1] : -1;    // the usual case: EOS below min_length
   // steps 1-2 of the distribution for column c holding xv: x'; -inf: not selectable
   auto penalised = [&](float xv, int c) -> float {
@@ -200,6 +263,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
     for (int b = 2; b < n_banned; ++b) ban |= (banned[b] == c);
     if (ban) return -__builtin_inff();
     float v = xv;
+    if constexpr (BEAM) v = FAST ? v - (lse_mx + lse_lg) : (v - lse_mx) - lse_lg;
     if constexpr (HIST) {
       if ((hbits[c >> 5] >> (c & 31)) & 1u) v = v < 0.f ? v * penalty : v / penalty;
     }
@@ -267,6 +331,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
     });
   }, bins, wt_i, res);
   if (sel.total == 0) {                                            // nothing selectable (block-uniform)
+    if constexpr (BEAM) {
+      if (t < bd.K) {
+        bd.out_key[(size_t)row * bd.K + t] = -__builtin_inff(), out_val[(size_t)row * bd.K + t] = -__builtin_inff();
+        out_idx[(size_t)row * bd.K + t] = SAMPLE_NONE;
+      }
+      return;
+    }
     if (t == 0) {
       out_val[(size_t)row * 2] = -__builtin_inff(), out_idx[(size_t)row * 2] = 0;
       out_val[(size_t)row * 2 + 1] = -__builtin_inff(), out_idx[(size_t)row * 2 + 1] = SAMPLE_NONE;
@@ -337,10 +408,40 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
     if (t == 0) s_stat[0] = sfx;
     __syncthreads();
     const float cut = (1.f - top_p) * s_stat[0];
-    if (t >= 1 && t < n && sfx <= cut) atomicMin(&s_keep, t);
+    if (t >= (BEAM ? 2 : 1) && t < n && sfx <= cut) atomicMin(&s_keep, t);     // (BEAM: min_tokens_to_keep = 2)
     __syncthreads();
   }
   const int n_keep = s_keep;
+  if constexpr (BEAM) {
+    // ---- e'. the kept entries' accumulated scores and Gumbel keys; the row's K best by (key descending, id ascending)
+    float a = -__builtin_inff(), key = -__builtin_inff();
+    int id = SAMPLE_NONE;
+    if (t < n_keep) {
+      id = sort_i[t];
+      a = sort_v[t] + bd.run_scores[row];
+      const uint64_t kk = (uint64_t)bd.seed[0] ^ ((uint64_t)(uint32_t)bd.ctl[0] * 0x9E3779B97F4A7C15ull);
+      const uint64_t z = sample_mix64(kk + ((uint64_t)row * (uint64_t)V + (uint64_t)id) * 0xD1B54A32D192ED03ull);
+      const float uu = ((float)(uint32_t)(z >> 41) + 0.5f) * 0x1p-23f;
+      key = a + -logf(-logf(uu));
+      id_w[t] = key;
+    }
+    __syncthreads();
+    if (t < n_keep) {
+      int rank = 0;
+      for (int d = 0; d < n_keep; ++d) {
+        const float dk = id_w[d];
+        rank += (dk > key || (dk == key && sort_i[d] < id)) ? 1 : 0;
+      }
+      if (rank < bd.K) {
+        bd.out_key[(size_t)row * bd.K + rank] = key, out_val[(size_t)row * bd.K + rank] = a;
+        out_idx[(size_t)row * bd.K + rank] = min(max(id, 0), V - 1);
+      }
+    } else if (t < bd.K) {                                         // (ranks n_keep .. K - 1: fewer survivors than K)
+      bd.out_key[(size_t)row * bd.K + t] = -__builtin_inff(), out_val[(size_t)row * bd.K + t] = -__builtin_inff();
+      out_idx[(size_t)row * bd.K + t] = SAMPLE_NONE;
+    }
+    return;
+  }
   // ---- e. the kept entries in id order, their prefix sums, the pick
   if (t < n_keep) {
     const int id = sort_i[t];
@@ -377,13 +478,38 @@ int sample_rows_launch(const T* logits, int ld, int M, int V, const float* u, co
     return TASU_ERR_ARG;
   if (hist) {
     if (!hist_len || hist_ld <= 0 || !(penalty > 0.f)) return TASU_ERR_ARG;
-    TASU_LAUNCH((sample_rows_kernel<T, true>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, u, banned, n_banned, hist, hist_ld,
-                hist_len, penalty, temperature, top_k, top_p, out_val, out_idx);
+    TASU_LAUNCH((sample_rows_kernel<T, true, false>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, u, banned, n_banned, hist, hist_ld,
+                hist_len, penalty, temperature, top_k, top_p, out_val, out_idx, BeamDraw{});
     return TASU_OK;
   }
   if (penalty != 1.f) return TASU_ERR_ARG;                         // a penalty needs the history
-  TASU_LAUNCH((sample_rows_kernel<T, false>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, u, banned, n_banned, hist, hist_ld,
-              hist_len, penalty, temperature, top_k, top_p, out_val, out_idx);
+  TASU_LAUNCH((sample_rows_kernel<T, false, false>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, u, banned, n_banned, hist, hist_ld,
+              hist_len, penalty, temperature, top_k, top_p, out_val, out_idx, BeamDraw{});
+  return TASU_OK;
+}
+
+template <typename T>
+int beam_sample_rows_launch(const T* logits, int ld, int M, int V, int K, int n_beams, int first, const int64_t* seed, const int32_t* ctl,
+                            const float* run_scores, const int32_t* banned, int n_banned, const int32_t* hist, int hist_ld,
+                            const int32_t* hist_len, float penalty, float temperature, int top_k, float top_p, float* out_key,
+                            float* out_val, int32_t* out_idx, hipStream_t stream) {
+  constexpr int VEC = SampleVec<T>::VEC;
+  if (!logits || !seed || !ctl || !run_scores || !out_key || !out_val || !out_idx || M <= 0 || M > SAMPLE_MAX_M || V <= 0 ||
+      V > SAMPLE_MAX_V || ld < V || ld % VEC || ((uintptr_t)logits & 15) || n_banned < 0 || (n_banned > 0 && !banned) || top_k < 1 ||
+      top_k > SAMPLE_POOL || !(temperature > 0.f) || !(temperature < __builtin_inff()) || !(top_p >= 0.f) || K < 1 || K > 32 ||
+      n_beams < 1 || M % n_beams || (first != 0 && first != 1))
+    return TASU_ERR_ARG;
+  if (top_k < 2) top_k = 2;                                        // HF: min_tokens_to_keep = 2 with more than one beam
+  const BeamDraw bd{seed, ctl, run_scores, out_key, n_beams, first, K};
+  if (hist) {
+    if (!hist_len || hist_ld <= 0 || !(penalty > 0.f)) return TASU_ERR_ARG;
+    TASU_LAUNCH((sample_rows_kernel<T, true, true>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, (const float*)nullptr, banned, n_banned,
+                hist, hist_ld, hist_len, penalty, temperature, top_k, top_p, out_val, out_idx, bd);
+    return TASU_OK;
+  }
+  if (penalty != 1.f) return TASU_ERR_ARG;                         // a penalty needs the history
+  TASU_LAUNCH((sample_rows_kernel<T, false, true>), dim3(M), dim3(SAMPLE_THREADS), 0, stream, logits, ld, V, (const float*)nullptr, banned, n_banned,
+              hist, hist_ld, hist_len, penalty, temperature, top_k, top_p, out_val, out_idx, bd);
   return TASU_OK;
 }
 }  // namespace
@@ -406,4 +532,21 @@ extern "C" int tasu_f32_sample_rows(const float* logits, int ld, int M, int V, c
                                     float top_p, float* out_val, int32_t* out_idx, void* stream) {
   return sample_rows_launch<float>(logits, ld, M, V, u, banned, n_banned, hist, hist_ld, hist_len, penalty, temperature, top_k, top_p,
                                    out_val, out_idx, (hipStream_t)stream);
+}
+
+extern "C" int tasu_beam_sample_rows(const void* logits, int ld, int M, int V, int K, int n_beams, int first, const int64_t* seed,
+                                     const int32_t* ctl, const float* run_scores, const int32_t* banned, int n_banned,
+                                     const int32_t* hist, int hist_ld, const int32_t* hist_len, float penalty, float temperature,
+                                     int top_k, float top_p, float* out_key, float* out_val, int32_t* out_idx, void* stream) {
+  return beam_sample_rows_launch<bf16>((const bf16*)logits, ld, M, V, K, n_beams, first, seed, ctl, run_scores, banned, n_banned, hist,
+                                       hist_ld, hist_len, penalty, temperature, top_k, top_p, out_key, out_val, out_idx,
+                                       (hipStream_t)stream);
+}
+
+extern "C" int tasu_f32_beam_sample_rows(const float* logits, int ld, int M, int V, int K, int n_beams, int first, const int64_t* seed,
+                                         const int32_t* ctl, const float* run_scores, const int32_t* banned, int n_banned,
+                                         const int32_t* hist, int hist_ld, const int32_t* hist_len, float penalty, float temperature,
+                                         int top_k, float top_p, float* out_key, float* out_val, int32_t* out_idx, void* stream) {
+  return beam_sample_rows_launch<float>(logits, ld, M, V, K, n_beams, first, seed, ctl, run_scores, banned, n_banned, hist, hist_ld,
+                                        hist_len, penalty, temperature, top_k, top_p, out_key, out_val, out_idx, (hipStream_t)stream);
 }

@@ -6,6 +6,9 @@ rows' 2*nb best log-probs, finished-hypothesis heap, early-stop heuristic, and t
 positions), so a generated position is ONE hipGraph replay with no host round trip; the host only polls a pinned
 "done" word a couple of steps behind the device and walks the back-pointers once at the end.  ``BeamState`` is the
 vectorised host restatement of the same bookkeeping (tests pin it against the oracle's loop, and the kernel against it).
+``do_sample=True`` takes the top-k's place in the same loop: one sampled token per row at one beam (``tasu_sample_rows``), every beam
+row's 2*nb drawn candidates and the update that selects by their Gumbel keys at more (``tasu_beam_sample_rows``,
+``tasu_beam_update_drawn``: HF's beam-search multinomial sampling; ``BeamState.update_drawn``).
 
 Device per step (M = B*nb rows): beam reorder of the cache's row index -> embedding rows -> 28 x [RMSNorm, qkv GEMM, RoPE,
 KV append, cache attention, o GEMM + residual, RMSNorm, gate|up GEMM, SwiGLU, down GEMM + residual] -> RMSNorm -> lm_head
@@ -33,7 +36,7 @@ def check_repetition_penalty(penalty):
     return penalty
 
 
-Sampling = collections.namedtuple("Sampling", "temperature top_k top_p")   # generate(do_sample=True, num_beams=1): the warpers' knobs
+Sampling = collections.namedtuple("Sampling", "temperature top_k top_p")   # generate(do_sample=True): the warpers' knobs
 
 
 def check_sampling(temperature=1.0, top_k=50, top_p=1.0):
@@ -86,9 +89,12 @@ class BeamState:
         flat_beam = np.repeat(np.arange(nb), K)[None, :].repeat(B, 0)
         # top-K of the batch's candidates; ties resolved like a flattened [nb * V] top-k (beam, then token id)
         order = np.lexsort((flat_tok, flat_beam, -flat), axis=-1)[:, :K]
-        top_lp = np.take_along_axis(flat, order, 1)
-        tok = np.take_along_axis(flat_tok, order, 1)
-        beam = np.take_along_axis(flat_beam, order, 1)
+        return self._select(np.take_along_axis(flat, order, 1), np.take_along_axis(flat_tok, order, 1),
+                            np.take_along_axis(flat_beam, order, 1))
+
+    def _select(self, top_lp, tok, beam):
+        """The update on an utterance's K candidates in their order: accumulated scores, tokens, parent beams [B, K]."""
+        B, nb, K, cur = self.B, self.nb, self.K, self.cur
         cand = np.take_along_axis(self.run_seq, beam[:, :, None], 1).copy()
         cand[:, :, cur] = tok
         stop = (tok == self.eos) | (cur + 1 >= self.max_new)
@@ -117,6 +123,22 @@ class BeamState:
         self.unsat = self.unsat & (best_run > worst_fin).any(-1)
         self.done = not (self.unsat.any() and not stop.all())
         return next_tok, next_parent
+
+    def update_drawn(self, key, a, tok):
+        """Beam-sample (HF ``_beam_search`` with do_sample): key / a / tok [B, nb, K], per row the K candidates with the largest Gumbel
+        keys, their ACCUMULATED scores and tokens (tasu_beam_sample_rows; a filler token 0x7fffffff counts as token 0 at -inf).  The
+        utterance's K candidates are its K largest keys in the order (key desc, beam, token) -- the draw order; the rest is ``update``'s
+        on (a, beam, token) in that order."""
+        B, nb, K = self.B, self.nb, self.K
+        flat_tok = np.asarray(tok).reshape(B, nb * K).astype(np.int64)
+        real = (flat_tok >= 0) & (flat_tok != 0x7fffffff)
+        flat_key = np.where(real, np.asarray(key, dtype=np.float32).reshape(B, nb * K), np.float32(-np.inf))
+        flat = np.where(real, np.asarray(a, dtype=np.float32).reshape(B, nb * K), np.float32(-np.inf))
+        flat_tok = np.where(real, flat_tok, 0)
+        flat_beam = np.repeat(np.arange(nb), K)[None, :].repeat(B, 0)
+        order = np.lexsort((flat_tok, flat_beam, -flat_key), axis=-1)[:, :K]
+        return self._select(np.take_along_axis(flat, order, 1), np.take_along_axis(flat_tok, order, 1),
+                            np.take_along_axis(flat_beam, order, 1))
 
     def result(self):
         n = int(self.fin_len[:, 0].max())
@@ -158,7 +180,7 @@ class DeviceBeam:
             # and the position counter ctl[0] are device words the uniform kernel reads, so a replayed graph draws new numbers
             seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64))
             self.seed = up("smp_seed", np.array([seed], dtype=np.int64))
-            self.u = buf("smp_u", (M,), torch.float32)
+            self.u = buf("smp_u", (M,), torch.float32)               # (one beam: the rows' uniforms; beam-sample hashes per column)
         self.hist = self.hist_len = None
         if self.penalty != 1.0:
             # generated tokens of every beam row (tasu_beam_hist_update keeps them next to the beam state): what HF's
@@ -227,7 +249,7 @@ def check_kv_cache_fits(model, B, nb, ctx, elem_bytes, names):
 
 def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_token_id, pad_token_id, max_ctx, attention,
                   repetition_penalty=1.0, kv_elem_bytes=2, kv_names=("dec_kc", "dec_vc"), sampling=None,
-                  sample_ops=("sample_uniform", "sample_rows")):
+                  sample_ops=("sample_uniform", "sample_rows"), beam_sample_ops=("beam_sample_rows", "beam_update_drawn")):
     """Checks a generate() call against the limits of the device beam search (tasu_beam_update: include/tasu_hip.h), the context
     limit ``max_ctx`` of the caller's cache attention and the device's free memory (the KV caches ``kv_names``), BEFORE any
     prefill.  Returns (min_length in generated positions, eos, pad)."""
@@ -241,16 +263,16 @@ def generate_args(model, st: StepState, nb, max_new_tokens, min_length, eos_toke
     if S + max_new_tokens > max_ctx:
         raise ValueError(f"prompt {S} + max_new_tokens {max_new_tokens} exceeds {attention} context limit {max_ctx}")
     if sampling is not None:                              # do_sample=True: raised before any prefill work, like the penalty's
-        if nb != 1:
-            raise NotImplementedError(f"generate(do_sample=True, num_beams={nb}): sampling is served at num_beams=1 only (beam-sample is "
-                                      "not built)")
+        if nb != 1 and not all(hasattr(model.ops, n) for n in beam_sample_ops):
+            raise NotImplementedError(f"generate(do_sample=True, num_beams={nb}): the ops backend {type(model.ops).__name__} has no "
+                                      f"beam-sample kernels ({', '.join(beam_sample_ops)}); it serves do_sample=True at num_beams=1 only")
         if sampling.top_k == 0:
             raise NotImplementedError("generate(do_sample=True, top_k=0): whole-vocabulary sampling is not built; the sampler keeps the "
                                       f"top_k best tokens of a row in a pool of {SAMPLE_POOL}, 1 <= top_k <= {SAMPLE_POOL}")
         if sampling.top_k > SAMPLE_POOL:
             raise NotImplementedError(f"generate(do_sample=True, top_k={sampling.top_k}): the sampler's candidate pool holds "
                                       f"{SAMPLE_POOL} tokens per row, 1 <= top_k <= {SAMPLE_POOL}")
-        if not all(hasattr(model.ops, n) for n in sample_ops):
+        if nb == 1 and not all(hasattr(model.ops, n) for n in sample_ops):
             raise NotImplementedError(f"generate(do_sample=True): the ops backend {type(model.ops).__name__} has no sampling kernels "
                                       f"({', '.join(sample_ops)})")
     if check_repetition_penalty(repetition_penalty) != 1.0:
@@ -320,7 +342,8 @@ def decode_positions(model, bs: DeviceBeam, device_step, pad, tag):
 def beam_search_generate(model, st: StepState, num_beams=4, max_new_tokens=200, min_length=1, length_penalty=1.0,
                          eos_token_id=None, pad_token_id=None, repetition_penalty=1.0, sampling=None):
     """st: a prepared state whose projector output (st.dev['y2']) is ready.  ``sampling``: a Sampling (check_sampling) for
-    generate(do_sample=True, num_beams=1), None for beam search / greedy.  Returns LongTensor [B, n_new] (CPU)."""
+    generate(do_sample=True) (one beam: multinomial sampling; more: beam-sample), None for beam search / greedy.  Returns LongTensor
+    [B, n_new] (CPU)."""
     if model.lora is not None and model._lora_run is not None:
         # use_peft: prefill and the decode loop run on the merged weights W + s B A (ps_slm_amd/lora.py: merged_llm)
         from .lora import merged_llm
@@ -421,6 +444,7 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     ops.gemm(xn, llm.head, logits, B, V, D)
     tv = buf("dec_topv", (M, K), f32)
     ti = buf("dec_topi", (M, K), i32)
+    tkey = buf("dec_topkey", (M, K), f32) if sampling is not None and nb > 1 else None      # beam-sample: the candidates' keys
     bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty, sampling)
     penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
 
@@ -428,7 +452,14 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
         """Per-row top-k and the beam update; under a repetition penalty the top-k reads every row's token history and the
         history follows the beams after the update (``repetition_penalty == 1.0``: exactly the launches without the knob).
         do_sample: the position's uniforms and one sampled token per row take the top-k's place (``do_sample=False``: exactly the
-        launches without the knob)."""
+        launches without the knob).  do_sample with more than one beam: every beam row's K = 2 nb drawn candidates (at the first
+        position too: nb rows per utterance read its one logits row) and the update that selects by their keys."""
+        if tkey is not None:
+            ops.beam_sample_rows(logits, M, V, K, first, bs, 1, sampling.temperature, sampling.top_k, sampling.top_p, tkey, tv, ti)
+            ops.beam_update_drawn(tkey, tv, ti, bs)
+            if penalised:
+                ops.beam_hist_update(bs)
+            return
         if sampling is not None:
             ops.sample_uniform(bs.seed, bs.ctl, rows, bs.u)
             ops.sample_rows(logits, rows, V, bs.u, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, sampling.temperature, sampling.top_k,

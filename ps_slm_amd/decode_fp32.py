@@ -248,7 +248,8 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     _need_f32(model)
     min_length, eos, pad = generate_args(model, st, num_beams, max_new_tokens, min_length, eos_token_id, pad_token_id, F32_MAX_CTX,
                                          "the fp32 attention's", repetition_penalty, kv_elem_bytes=4, kv_names=("f32_kc", "f32_vc"),
-                                         sampling=sampling, sample_ops=("sample_uniform", "f32_sample_rows"))
+                                         sampling=sampling, sample_ops=("sample_uniform", "f32_sample_rows"),
+                                         beam_sample_ops=("f32_beam_sample_rows", "beam_update_drawn"))
     B, S, nb = st.B, st.S, num_beams
     ctx = S + max_new_tokens
     M, K = B * nb, 2 * nb
@@ -275,12 +276,19 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     ops.embed_rows(xn0, last_rows, xn, B, D)                    # the final-normed last prompt position of every utterance
     ops.f32_gemm(xn, weights_f32(model)["head"], logits, B, V, D, ws=ws)
     tv, ti = buf("dec_topv", (M, K), f32), buf("dec_topi", (M, K), i32)
+    tkey = buf("dec_topkey", (M, K), f32) if sampling is not None and nb > 1 else None      # beam-sample: the candidates' keys
     bs = DeviceBeam(model, B, nb, max_new_tokens, eos, length_penalty, min_length, S, valid, repetition_penalty, sampling)
     topk_ws = buf("f32_topk_ws", (M * 16 * (2 + 2 * K),), f32)               # the row split over 16 workgroups (tasu_f32_logprob_topk)
     penalised, pmode = bs.penalty != 1.0, penalty_mode(nb)
 
     def topk_and_update(rows, first):
         """decode.py's topk_and_update on the fp32 logits (``repetition_penalty == 1.0``: exactly the launches without the knob)."""
+        if tkey is not None:
+            ops.f32_beam_sample_rows(logits, M, V, K, first, bs, 1, sampling.temperature, sampling.top_k, sampling.top_p, tkey, tv, ti)
+            ops.beam_update_drawn(tkey, tv, ti, bs)
+            if penalised:
+                ops.beam_hist_update(bs)
+            return
         if sampling is not None:
             ops.sample_uniform(bs.seed, bs.ctl, rows, bs.u)
             ops.f32_sample_rows(logits, rows, V, bs.u, bs.banned, 1, bs.hist, bs.hist_len, bs.penalty, sampling.temperature, sampling.top_k,

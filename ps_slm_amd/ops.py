@@ -768,6 +768,33 @@ class HipOps:
         self._sample_rows(self.lib.tasu_f32_sample_rows, "tasu_f32_sample_rows", logits, M, V, u, banned, n_banned, hist, hist_len, penalty,
                           temperature, top_k, top_p, out_val, out_idx)
 
+    def _beam_sample_rows(self, fn, name, logits, M, V, K, first, bs, n_banned, temperature, top_k, top_p, out_key, out_val, out_idx):
+        hist = bs.hist
+        self._chk(fn(_p(logits), logits.stride(0), M, V, K, bs.nb, int(first), _p(bs.seed), _p(bs.ctl), _p(bs.run_scores), _p(bs.banned),
+                     n_banned, _p(hist), hist.stride(0) if hist is not None else 0, _p(bs.hist_len), float(bs.penalty), float(temperature),
+                     int(top_k), float(top_p), _p(out_key), _p(out_val), _p(out_idx), self._stream()), name)
+
+    def beam_sample_rows(self, logits, M, V, K, first, bs, n_banned, temperature, top_k, top_p, out_key, out_val, out_idx):
+        """Beam-sample candidates of M = B * nb rows of bf16 logits (``first``: B rows of logits): per row the K largest Gumbel keys,
+        their accumulated scores and tokens, [M, K] each (tasu_beam_sample_rows); seed, position, running scores, ban and history are
+        ``bs``'s device buffers (ps_slm_amd.decode.DeviceBeam)."""
+        self._beam_sample_rows(self.lib.tasu_beam_sample_rows, "tasu_beam_sample_rows", logits, M, V, K, first, bs, n_banned, temperature,
+                               top_k, top_p, out_key, out_val, out_idx)
+
+    def f32_beam_sample_rows(self, logits, M, V, K, first, bs, n_banned, temperature, top_k, top_p, out_key, out_val, out_idx):
+        """beam_sample_rows on fp32 logits (tasu_f32_beam_sample_rows)."""
+        self._beam_sample_rows(self.lib.tasu_f32_beam_sample_rows, "tasu_f32_beam_sample_rows", logits, M, V, K, first, bs, n_banned,
+                               temperature, top_k, top_p, out_key, out_val, out_idx)
+
+    def beam_update_drawn(self, keys, vals, idx, bs):
+        """One position of the device-side beam search on drawn candidates (tasu_beam_update_drawn); ``bs``: DeviceBeam."""
+        self._chk(self.lib.tasu_beam_update_drawn(_p(keys), _p(vals), _p(idx), _p(bs.run_scores), _p(bs.fin_scores), _p(bs.fin_len),
+                                                  _p(bs.fin_par), _p(bs.fin_tok), _p(bs.is_fin), _p(bs.unsat), _p(bs.bp_tok), _p(bs.bp_par),
+                                                  _p(bs.len_pow), _p(bs.ctl), _p(bs.done_host), _p(bs.valid), _p(bs.next_ids),
+                                                  _p(bs.next_src), _p(bs.next_pos), _p(bs.next_slot), _p(bs.next_lens), _p(bs.banned),
+                                                  bs.B, bs.nb, bs.max_new, bs.eos, bs.min_length, bs.S, self._stream()),
+                  "tasu_beam_update_drawn")
+
     def beam_hist_update(self, bs):
         """Every beam row's token history after beam_update (tasu_beam_hist_update); ``bs``: ps_slm_amd.decode.DeviceBeam."""
         self._chk(self.lib.tasu_beam_hist_update(_p(bs.hist), _p(bs.hist_len), _p(bs.ctl), _p(bs.next_src), _p(bs.next_ids), bs.B, bs.nb,

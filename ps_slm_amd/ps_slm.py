@@ -648,23 +648,23 @@ class slam_model_asr:
         from ps_slm_amd.decode import beam_search_generate
         core = self.core
         self._refresh_if_touched()
-        # the decode loop is HF beam search / greedy with do_sample=False (ps-slm.py:660-675 defaults) or HF sampling at num_beams=1
-        # (do_sample=True: csrc/sample.hip); repetition_penalty is served on all of them (ps_slm_amd/decode.py, HF's processor).  A
-        # sampling knob HF would silently ignore (no do_sample) and beam-sample (do_sample with num_beams > 1) are rejected
+        # the decode loop is HF beam search / greedy with do_sample=False (ps-slm.py:660-675 defaults) or, with do_sample=True, HF multinomial
+        # sampling (num_beams=1) and beam-search multinomial sampling (num_beams > 1, the reference's default 4 included:
+        # csrc/sample.hip); repetition_penalty is served on all of them (ps_slm_amd/decode.py, HF's processor).  A sampling knob HF would
+        # silently ignore (no do_sample) is rejected
         from ps_slm_amd.decode import check_repetition_penalty, check_sampling
         repetition_penalty = check_repetition_penalty(kwargs.get("repetition_penalty", 1.0))
         num_beams = kwargs.get("num_beams", 4)
         sampling = None
-        if kwargs.get("do_sample", False) is True and num_beams == 1:
+        if kwargs.get("do_sample", False) is True:
             sampling = check_sampling(kwargs.get("temperature", 1.0), kwargs.get("top_k", default_top_k(self.model_config)),
                                       kwargs.get("top_p", 1.0))
         else:
             for name, default in (("do_sample", False), ("top_p", 1.0), ("temperature", 1.0), ("top_k", None)):
                 if kwargs.get(name, default) != default:
                     raise NotImplementedError(f"generate({name}={kwargs[name]!r}, num_beams={num_beams!r}): the MI355X decode loop serves "
-                                              "the sampling knobs as do_sample=True with num_beams=1 only (Multitask/model/ps-slm.py:"
-                                              f"660-675); {name} without do_sample=True would silently be ignored, and beam-sample "
-                                              "(do_sample=True with num_beams > 1) is not built")
+                                              "the sampling knobs with do_sample=True only (Multitask/model/ps-slm.py:660-675); "
+                                              f"{name} without do_sample=True would silently be ignored")
         if self.gt_emb:                                     # ps-slm.py:590-598
             texts = [re.sub(r"[^A-Za-z\s.,!?]+", "", t).lower().strip() for t in targets]
             ids_list = [self.encoder_tokenizer.encode(t) for t in texts]

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 24
+#define TASU_ABI_VERSION 25
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -558,6 +558,25 @@ int tasu_kv_append(const void* qkv, void* kcache, void* vcache, const int32_t* p
  * [M, 64] from tasu_rope_table) and write the rotated k and v to cache[row, pos[row]] -- tasu_rope_fwd + kv_append. */
 int tasu_rope_append(void* qkv, const float* cos_tab, const float* sin_tab, void* kcache, void* vcache, const int32_t* pos,
                      int M, int H, int G, int ctx, void* stream);
+/* Qwen3's per-head q/k RMSNorm (modeling_qwen3.py: Qwen3Attention.q_norm / k_norm) between the q|k|v projection and the rotary
+ * embedding (csrc/qk_norm.hip).  pre / out / dqkv / qkv: bf16 [M, (H+2G)*128]; wq / wk: fp32 [128], the layer's q_norm / k_norm
+ * weight; cos / sin: fp32 [M, 64] from tasu_rope_table; rstd: fp32 [M, H+G] (q heads, then k heads).  bf16-autocast arithmetic:
+ * r = rsqrt(mean_128(pre^2) + eps) and pre * r in fp32, ONE rounding to bf16, times the fp32 weight and rotated in fp32, ONE
+ * rounding at the store.  Every pointer but rstd and pos is accessed in 16-byte vectors: a misaligned one is TASU_ERR_ARG, as are
+ * H % G != 0 and non-positive sizes, before any launch.
+ *   fwd:    out = rope(norm(pre)) on the q and k heads, v heads copied bit for bit; out == pre is allowed (any other overlap is
+ *           refused); rstd may be NULL when no backward follows.
+ *   bwd:    in place on dqkv (g = the gradient w.r.t. the normed, weighted, UNROTATED head: what tasu_attn_bwd_rope leaves):
+ *           dpre = r (w g - xn mean_128(w g xn)), xn = pre r in fp32 (the rounding of xn taken as the identity); v block untouched.
+ *   append: the forward in place on the decode step's single-token qkv, then the rotated k and v -> cache[row, pos[row]]
+ *           (tasu_rope_append's contract; a pos outside [0, ctx) writes nothing to the cache).  Same device function as fwd: a
+ *           key appended at decode time has the bits of the same key out of a prefill. */
+int tasu_qk_norm_rope_fwd(const void* pre, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab, void* out,
+                          float* rstd, int M, int H, int G, float eps, void* stream);
+int tasu_qk_norm_bwd(void* dqkv, const void* pre, const float* wq, const float* wk, const float* rstd, int M, int H, int G,
+                     void* stream);
+int tasu_qk_norm_rope_append(void* qkv, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab, void* kcache,
+                             void* vcache, const int32_t* pos, int M, int H, int G, int ctx, float eps, void* stream);
 /* index[m, i] = (m / n_beams) * n_beams for i < S (shared prompt), m for i >= S. */
 int tasu_kv_index_init(int32_t* index, int B, int n_beams, int S, int ctx, void* stream);
 /* dst[m, :lens[m]] = src[src_row[m], :lens[m]] (src_row NULL = identity); dst != src; entries >= lens[m] untouched. */

@@ -86,6 +86,9 @@ PROTOTYPES = {
     "tasu_gemm_skinny_qkv_rope": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp],
     "tasu_gemm_skinny_swiglu": [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i64, vp],
     "tasu_rope_append": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "tasu_qk_norm_rope_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+    "tasu_qk_norm_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "tasu_qk_norm_rope_append": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "tasu_kv_index_init": [vp, i32, i32, i32, i32, vp],
     "tasu_kv_index_reorder": [vp, vp, vp, vp, i32, i32, vp],
     "tasu_attn_decode": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
@@ -190,7 +193,7 @@ PROTOTYPES.update({
     "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm_dispatch.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

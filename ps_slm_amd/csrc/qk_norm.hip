@@ -1,0 +1,181 @@
+// Per-head q/k RMSNorm of the Qwen3 decoders (modeling_qwen3.py: Qwen3Attention.q_norm / k_norm, a Qwen3RMSNorm over each 128-wide
+// head) between the q|k|v projection and the rotary embedding -- the step none of the fused q|k|v + RoPE GEMM epilogues can take.
+//
+//   tasu_qk_norm_rope_fwd      out = bf16(rope(w * bf16(pre * r))),  r = rsqrt(mean_128(pre^2) + eps), per row and q / k head;
+//                              v heads copied bit for bit; r kept for the backward
+//   tasu_qk_norm_bwd           dpre = r (w g - xn mean_128(w g xn)),  xn = pre r, in place on dqkv (g: what the attention backward
+//                              leaves there behind its own RoPE backward); v block untouched
+//   tasu_qk_norm_rope_append   the forward in place on the decode step's [M, (H+2G)*128], then k and v -> cache[row, pos[row]]
+//
+// bf16-autocast arithmetic of HF's Qwen3RMSNorm: the statistic and pre * r in fp32, ONE rounding to bf16 (the cast back to the
+// input dtype), the product with the fp32 weight and the rotation in fp32, ONE rounding at the store.
+//
+// Thread map: 16 lanes per (row, head), 8 contiguous elements (one 16-byte vector) per lane; lanes 0-7 hold dims 0..63, lanes 8-15
+// dims 64..127, so the rotate-half partner of a lane's vector is lane ^ 8's and the mean is four xor-shuffles inside the 16-lane
+// group.  A wave serves 4 heads, a 256-thread block 16; nothing goes through LDS, no atomics.  The forward and the append kernel
+// share qk_head_fwd: a key appended at decode time has the bits of the same key out of a prefill.
+//
+// Cost, DERIVED (not measured here): one read and one write of [M, (H+2G)*128] bf16 per launch (the v block only when out != pre).
+#include "common.h"
+#include "../../include/tasu_hip.h"
+
+namespace {
+
+constexpr int HD = 128;
+
+__device__ __forceinline__ float group16_sum(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One lane's share of one q / k head: x = its 8 elements of pre, w = the head's norm weight at those dims, (cs, sn) = the row's
+// table at the lane's 8 pair indices; sub = lane & 15.  Returns the rotated, rounded vector; r = the head's rstd (all 16 lanes).
+__device__ __forceinline__ bf16x8 qk_head_fwd(const bf16x8 x, const float* __restrict__ w, const float* __restrict__ cs,
+                                              const float* __restrict__ sn, float eps, int sub, float& r) {
+  float xf[8], ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    xf[j] = (float)x[j];
+    ss = __builtin_fmaf(xf[j], xf[j], ss);
+  }
+  ss = group16_sum(ss);
+  r = rsqrtf(ss * (1.0f / HD) + eps);
+  const f32x4 w0 = *(const f32x4*)w, w1 = *(const f32x4*)(w + 4);
+  const f32x4 c0 = *(const f32x4*)cs, c1 = *(const f32x4*)(cs + 4);
+  const f32x4 s0 = *(const f32x4*)sn, s1 = *(const f32x4*)(sn + 4);
+  const bool hi = sub >= 8;
+  bf16x8 out;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float wj = j < 4 ? w0[j & 3] : w1[j & 3];
+    const float c = j < 4 ? c0[j & 3] : c1[j & 3], s = j < 4 ? s0[j & 3] : s1[j & 3];
+    const float y = wj * bf16_round(xf[j] * r);            // w * x.to(bf16): fp32 product of the fp32 weight
+    const float other = __shfl_xor(y, 8, 64);              // the rotate-half partner (dim ^ 64)
+    float y1, y2;
+    rope_pair_f(hi ? other : y, hi ? y : other, c, s, y1, y2);
+    out[j] = (bf16)(hi ? y2 : y1);
+  }
+  return out;
+}
+
+__global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(const bf16* __restrict__ pre, const float* __restrict__ wq,
+                                                               const float* __restrict__ wk, const float* __restrict__ ct,
+                                                               const float* __restrict__ st, bf16* __restrict__ out,
+                                                               float* __restrict__ rstd, int M, int H, int G, float eps) {
+  const int NH = H + 2 * G, sub = threadIdx.x & 15;
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool live = unit < (long long)M * NH;
+  const int row = live ? (int)(unit / NH) : 0, hh = live ? (int)(unit % NH) : 0;
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 8;
+  if (hh >= H + G) {                                       // a v head: the projection's bits
+    if (live && out != pre) *(bf16x8*)(out + off) = *(const bf16x8*)(pre + off);
+    return;                                                // (whole 16-lane groups leave: the shuffles below stay inside a group)
+  }
+  const bf16x8 x = *(const bf16x8*)(pre + off);
+  const float* w = (hh < H ? wq : wk) + sub * 8;
+  const int p = (sub & 7) * 8;
+  float r;
+  const bf16x8 y = qk_head_fwd(x, w, ct + (size_t)row * 64 + p, st + (size_t)row * 64 + p, eps, sub, r);
+  if (!live) return;
+  *(bf16x8*)(out + off) = y;
+  if (rstd && sub == 0) rstd[(size_t)row * (H + G) + hh] = r;
+}
+
+__global__ __launch_bounds__(256) void qk_norm_bwd_kernel(bf16* __restrict__ dqkv, const bf16* __restrict__ pre,
+                                                          const float* __restrict__ wq, const float* __restrict__ wk,
+                                                          const float* __restrict__ rstd, int M, int H, int G) {
+  const int NH = H + 2 * G, NQK = H + G, sub = threadIdx.x & 15;
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // over the q and k heads only
+  const bool live = unit < (long long)M * NQK;
+  const int row = live ? (int)(unit / NQK) : 0, hh = live ? (int)(unit % NQK) : 0;
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 8;
+  const bf16x8 x = *(const bf16x8*)(pre + off), g = *(const bf16x8*)(dqkv + off);
+  const float* w = (hh < H ? wq : wk) + sub * 8;
+  const f32x4 w0 = *(const f32x4*)w, w1 = *(const f32x4*)(w + 4);
+  const float r = rstd[(size_t)row * NQK + hh];
+  float wg[8], xn[8], dot = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    wg[j] = (j < 4 ? w0[j & 3] : w1[j & 3]) * (float)g[j];
+    xn[j] = (float)x[j] * r;
+    dot = __builtin_fmaf(wg[j], xn[j], dot);
+  }
+  const float mean = group16_sum(dot) * (1.0f / HD);
+  bf16x8 d;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) d[j] = (bf16)(r * (wg[j] - xn[j] * mean));
+  if (live) *(bf16x8*)(dqkv + off) = d;
+}
+
+__global__ __launch_bounds__(256) void qk_norm_rope_append_kernel(bf16* __restrict__ qkv, const float* __restrict__ wq,
+                                                                  const float* __restrict__ wk, const float* __restrict__ ct,
+                                                                  const float* __restrict__ st, bf16* __restrict__ kc,
+                                                                  bf16* __restrict__ vc, const int32_t* __restrict__ pos, int M,
+                                                                  int H, int G, int ctx, float eps) {
+  const int NH = H + 2 * G, sub = threadIdx.x & 15;
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool live = unit < (long long)M * NH;
+  const int row = live ? (int)(unit / NH) : 0, hh = live ? (int)(unit % NH) : 0;
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 8;
+  const int at = pos[row];
+  const bool slot_ok = live && at >= 0 && at < ctx;        // a position outside the cache writes nothing there
+  const size_t slot = ((size_t)row * ctx + (slot_ok ? at : 0)) * ((size_t)G * HD);
+  if (hh >= H + G) {
+    if (slot_ok) *(bf16x8*)(vc + slot + (size_t)(hh - H - G) * HD + sub * 8) = *(const bf16x8*)(qkv + off);
+    return;
+  }
+  const bf16x8 x = *(const bf16x8*)(qkv + off);
+  const float* w = (hh < H ? wq : wk) + sub * 8;
+  const int p = (sub & 7) * 8;
+  float r;
+  const bf16x8 y = qk_head_fwd(x, w, ct + (size_t)row * 64 + p, st + (size_t)row * 64 + p, eps, sub, r);
+  if (!live) return;
+  *(bf16x8*)(qkv + off) = y;
+  if (hh >= H && slot_ok) *(bf16x8*)(kc + slot + (size_t)(hh - H) * HD + sub * 8) = y;
+}
+
+inline bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+inline bool shape_ok(int M, int H, int G) {
+  return M > 0 && H > 0 && G > 0 && H % G == 0 && (long long)M * (H + 2 * G) <= 0x7fffffffLL / 16;
+}
+inline unsigned blocks_for(long long units) { return (unsigned)((units + 15) / 16); }
+
+}  // namespace
+
+extern "C" int tasu_qk_norm_rope_fwd(const void* pre, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab,
+                                     void* out, float* rstd, int M, int H, int G, float eps, void* stream) {
+  if (!pre || !wq || !wk || !cos_tab || !sin_tab || !out || !shape_ok(M, H, G) || !(eps >= 0.f)) return TASU_ERR_ARG;
+  if (misaligned(pre) || misaligned(wq) || misaligned(wk) || misaligned(cos_tab) || misaligned(sin_tab) || misaligned(out))
+    return TASU_ERR_ARG;
+  if (out != pre) {                                        // the same buffer, or two that do not overlap
+    const size_t bytes = (size_t)M * (H + 2 * G) * HD * sizeof(bf16);
+    const uintptr_t a = (uintptr_t)pre, b = (uintptr_t)out;
+    if (a < b + bytes && b < a + bytes) return TASU_ERR_ARG;
+  }
+  TASU_LAUNCH(qk_norm_rope_fwd_kernel, dim3(blocks_for((long long)M * (H + 2 * G))), dim3(256), 0, (hipStream_t)stream,
+              (const bf16*)pre, wq, wk, cos_tab, sin_tab, (bf16*)out, rstd, M, H, G, eps);
+  return TASU_OK;
+}
+
+extern "C" int tasu_qk_norm_bwd(void* dqkv, const void* pre, const float* wq, const float* wk, const float* rstd, int M, int H,
+                                int G, void* stream) {
+  if (!dqkv || !pre || !wq || !wk || !rstd || dqkv == pre || !shape_ok(M, H, G)) return TASU_ERR_ARG;
+  if (misaligned(dqkv) || misaligned(pre) || misaligned(wq) || misaligned(wk)) return TASU_ERR_ARG;
+  TASU_LAUNCH(qk_norm_bwd_kernel, dim3(blocks_for((long long)M * (H + G))), dim3(256), 0, (hipStream_t)stream, (bf16*)dqkv,
+              (const bf16*)pre, wq, wk, rstd, M, H, G);
+  return TASU_OK;
+}
+
+extern "C" int tasu_qk_norm_rope_append(void* qkv, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab,
+                                        void* kcache, void* vcache, const int32_t* pos, int M, int H, int G, int ctx, float eps,
+                                        void* stream) {
+  if (!qkv || !wq || !wk || !cos_tab || !sin_tab || !kcache || !vcache || !pos || !shape_ok(M, H, G) || ctx <= 0 || !(eps >= 0.f))
+    return TASU_ERR_ARG;
+  if (misaligned(qkv) || misaligned(wq) || misaligned(wk) || misaligned(cos_tab) || misaligned(sin_tab) || misaligned(kcache) ||
+      misaligned(vcache))
+    return TASU_ERR_ARG;
+  TASU_LAUNCH(qk_norm_rope_append_kernel, dim3(blocks_for((long long)M * (H + 2 * G))), dim3(256), 0, (hipStream_t)stream,
+              (bf16*)qkv, wq, wk, cos_tab, sin_tab, (bf16*)kcache, (bf16*)vcache, pos, M, H, G, ctx, eps);
+  return TASU_OK;
+}

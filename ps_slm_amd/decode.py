@@ -384,7 +384,8 @@ def layers_per_gemm(ops, geo, layers, final_norm, x, x2, xn, qkv, ao, act, cos, 
     chunks = [(m0, min(64, M - m0)) for m0 in range(0, M, 64)]
     kcv, vcv = kc.view(L, M, ctx * W), vc.view(L, M, ctx * W)
     prenorm = bool(getattr(ops, "prenorm_ok", None) and ops.prenorm_ok(D, H * HD, I))
-    prenorm_in = bool(prenorm and ops.prenorm_in_ok(D, I) and len(chunks) <= 8)
+    # (Qwen3: the plain q|k|v GEMM reads a finished input norm -- the partial sums of squares have no consumer there)
+    prenorm_in = bool(prenorm and ops.prenorm_in_ok(D, I) and len(chunks) <= 8 and not geo.qk_norm)
     in_ssq = [None] * len(chunks)                                               # per chunk: the input norm's partial sums of squares
     if not normed:                                                               # (the step prologue has done it already)
         for m0, mc in chunks:
@@ -393,7 +394,11 @@ def layers_per_gemm(ops, geo, layers, final_norm, x, x2, xn, qkv, ao, act, cos, 
         next_norm = layers[l + 1]["ln1"] if l + 1 < L else final_norm            # the norm that consumes this layer's output
         for ci, (m0, mc) in enumerate(chunks):                                   # qkv projection + bias + RoPE + cache append
             r = slice(m0, m0 + mc)
-            if in_ssq[ci] is not None:        # xn = bf16(ln1 . x) from the previous layer's slab finish: rstd on the accumulators
+            if geo.qk_norm:                   # Qwen3: plain projection, then head norm + RoPE + cache append (csrc/qk_norm.hip)
+                ops.gemm_skinny(xn[r], w["wqkv"], qkv[r], mc, (H + 2 * G) * HD, D, ws)
+                ops.qk_norm_rope_append(qkv[r], w["q_norm"], w["k_norm"], cos[r], sin[r], kcv[l, r], vcv[l, r], slot[r], mc, H, G, ctx,
+                                        geo.rms_eps)
+            elif in_ssq[ci] is not None:      # xn = bf16(ln1 . x) from the previous layer's slab finish: rstd on the accumulators
                 ops.gemm_skinny_qkv_rope(xn[r], w["wqkv"], w["bqkv"], qkv[r], mc, H, G, D, cos[r], sin[r], kcv[l, r], vcv[l, r],
                                          slot[r], ctx, ws, sumsq=in_ssq[ci], eps=geo.rms_eps)
             else:
@@ -501,4 +506,5 @@ def _decode_after_prefill(model, st, nb, max_new_tokens, min_length, length_pena
     # the launch / layout switches decide which kernels device_step issues: a graph captured under one setting must not be
     # replayed under another (in-process A/B runs)
     switches = tuple(bool(getattr(ops, n, False)) for n in ("use_stream", "dec_frag", "dec_frag_act", "dec_down_slabs", "dec_prologue"))
-    return decode_positions(model, bs, device_step, pad, ("decode", switches))
+    # ... and so does the decoder family's q|k|v route (Qwen3: plain GEMM + head norm)
+    return decode_positions(model, bs, device_step, pad, ("decode", switches) + (("qk_norm",) if geo.qk_norm else ()))

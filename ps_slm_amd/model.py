@@ -52,6 +52,8 @@ class Geometry:
     rope_theta: float = 1e6
     rms_eps: float = 1e-6
     tied: bool = True
+    qk_norm: bool = False            # Qwen3: an RMSNorm over each 128-wide q and k head between the projection and the rotation
+    qkv_bias: bool = True            # Qwen2's q|k|v bias (Qwen3: attention_bias = false)
     # projector
     ctc_vocab: int = 25055
     bottleneck: int = 2048
@@ -87,6 +89,10 @@ class Geometry:
     def qwen25_7b(cls):
         return cls(llm_vocab=152064, llm_dim=3584, llm_inter=18944, llm_layers=28, llm_heads=28, llm_kv_heads=4,
                    tied=False)
+
+    @classmethod
+    def qwen3_1p7b(cls):
+        return cls(llm_dim=2048, llm_inter=6144, llm_layers=28, llm_heads=16, llm_kv_heads=8, qk_norm=True, qkv_bias=False)
 
     @classmethod
     def from_dict(cls, d):
@@ -264,8 +270,14 @@ class LLMWeights:
         wb = w.to(device=device, dtype=torch.bfloat16).contiguous()
         return wb, wb.t().contiguous()
 
-    def add_layer(self, ln1, wq, bq, wk, bk, wv, bv, wo, ln2, wg, wu, wd):
+    def add_layer(self, ln1, wq, bq, wk, bk, wv, bv, wo, ln2, wg, wu, wd, q_norm=None, k_norm=None):
+        """bq / bk / bv None: a decoder without q|k|v bias (Qwen3; a zero bias is kept for the consumers that read one).
+        q_norm / k_norm: Qwen3's per-head norm weights [128], kept in fp32."""
         dev = self.device
+        if self.geo.qk_norm and self.keep_f32:
+            raise NotImplementedError("a qk_norm (Qwen3) decoder in fp32 arithmetic: the fp32 kernel family has no q/k head norm")
+        if bq is None:
+            bq, bk, bv = (torch.zeros(w.shape[0], dtype=w.dtype, device=w.device) for w in (wq, wk, wv))
         wqkv, wqkv_t = self._pair(torch.cat([wq, wk, wv], 0), dev)
         wo_b, wo_t = self._pair(wo, dev)
         wgu, wgu_t = self._pair(torch.cat([wg, wu], 0), dev)
@@ -274,6 +286,10 @@ class LLMWeights:
             ln1=ln1.to(dev, torch.float32).contiguous(), ln2=ln2.to(dev, torch.float32).contiguous(),
             wqkv=wqkv, wqkv_t=wqkv_t, bqkv=torch.cat([bq, bk, bv], 0).to(dev, torch.bfloat16).contiguous(),
             wo=wo_b, wo_t=wo_t, wgu=wgu, wgu_t=wgu_t, wd=wd_b, wd_t=wd_t))
+        if self.geo.qk_norm:
+            if q_norm is None or k_norm is None or q_norm.numel() != HD or k_norm.numel() != HD:
+                raise KeyError(f"a qk_norm decoder needs self_attn.q_norm.weight / k_norm.weight [{HD}] in every layer")
+            self.layers[-1].update(q_norm=q_norm.to(dev, torch.float32).contiguous(), k_norm=k_norm.to(dev, torch.float32).contiguous())
         if self.keep_f32:
             if self.f32 is None:
                 self.f32 = {"layers": [], "head": None}
@@ -311,7 +327,10 @@ class LLMWeights:
         if hasattr(ops, "decode_frag_possible") and not ops.decode_frag_possible(geo.llm_dim, geo.llm_heads * HD):
             return
         for w in self.layers:
-            ops.register_decode_weight(w["wqkv"], "qkv", w["wqkv"].shape[0], geo.llm_heads, geo.llm_kv_heads)
+            if geo.qk_norm:                                 # a plain projection: the head norm sits between it and the rotation
+                ops.register_decode_weight(w["wqkv"], "plain", w["wqkv"].shape[0])
+            else:
+                ops.register_decode_weight(w["wqkv"], "qkv", w["wqkv"].shape[0], geo.llm_heads, geo.llm_kv_heads)
             ops.register_decode_weight(w["wo"], "plain", w["wo"].shape[0])
             ops.register_decode_weight(w["wgu"], "swiglu", geo.llm_inter)
             ops.register_decode_weight(w["wd"], "plain", w["wd"].shape[0], slabs_ok=True)
@@ -322,12 +341,14 @@ class LLMWeights:
         self._drop_weights()
         for l in range(geo.llm_layers):
             p = f"{pre}model.layers.{l}."
+            bias = (lambda m: sd[p + f"self_attn.{m}_proj.bias"]) if geo.qkv_bias else (lambda m: None)
             self.add_layer(sd[p + "input_layernorm.weight"],
-                           sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.q_proj.bias"],
-                           sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.k_proj.bias"],
-                           sd[p + "self_attn.v_proj.weight"], sd[p + "self_attn.v_proj.bias"],
+                           sd[p + "self_attn.q_proj.weight"], bias("q"),
+                           sd[p + "self_attn.k_proj.weight"], bias("k"),
+                           sd[p + "self_attn.v_proj.weight"], bias("v"),
                            sd[p + "self_attn.o_proj.weight"], sd[p + "post_attention_layernorm.weight"],
-                           sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"], sd[p + "mlp.down_proj.weight"])
+                           sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"], sd[p + "mlp.down_proj.weight"],
+                           sd.get(p + "self_attn.q_norm.weight"), sd.get(p + "self_attn.k_norm.weight"))
         emb = sd[pre + "model.embed_tokens.weight"]
         head = sd.get(pre + "lm_head.weight", emb)
         self.set_embed(emb, head, sd[pre + "model.norm.weight"])
@@ -344,9 +365,12 @@ class LLMWeights:
             return torch.randn(*shape, generator=g, device=dev, dtype=torch.float32) * 0.02
 
         ones = torch.ones(D, device=dev)
+        # Qwen3's head norms: 1 + 0.5 N(0, 1) instead of HF's ones, so that the two weights and their order matter in every run
+        qk = (lambda: dict(q_norm=1.0 + 25.0 * rn(HD), k_norm=1.0 + 25.0 * rn(HD))) if geo.qk_norm else dict
+        bias = (lambda n: rn(n)) if geo.qkv_bias else (lambda n: None)    # (no draw for a bias the decoder does not have)
         for _ in range(geo.llm_layers):
-            self.add_layer(ones, rn(H * HD, D), rn(H * HD), rn(G * HD, D), rn(G * HD), rn(G * HD, D), rn(G * HD),
-                           rn(D, H * HD), ones, rn(I, D), rn(I, D), rn(D, I))
+            self.add_layer(ones, rn(H * HD, D), bias(H * HD), rn(G * HD, D), bias(G * HD), rn(G * HD, D), bias(G * HD),
+                           rn(D, H * HD), ones, rn(I, D), rn(I, D), rn(D, I), **qk())
         emb = rn(geo.llm_vocab, D)
         self.set_embed(emb, emb if geo.tied else rn(geo.llm_vocab, D), ones)
 
@@ -590,6 +614,8 @@ class TasuModel:
         from .full_ft import LLMTrainables
         if self.full_ft is not None:
             raise RuntimeError("the LLM is already trainable on this model")
+        if self.geo.qk_norm:
+            raise NotImplementedError("freeze_llm=false on a qk_norm (Qwen3) decoder: the head norms' weight gradients are not built")
         if self.lora is not None or self.embed_base is not None:
             raise RuntimeError("enable_llm_training with LoRA / use_emb: freeze_llm=false with use_peft=true is the LoRA recipe (peft freezes the base weights)")
         if self.arith_train == "fp32" and not self.f32_wgrad_served:
@@ -762,6 +788,9 @@ class TasuModel:
         from .lora import LoraParams, LoraRunner
         if self.lora is not None:
             raise RuntimeError("LoRA is already enabled on this model")
+        if self.geo.qk_norm:
+            raise NotImplementedError("use_peft on a qk_norm (Qwen3) decoder: the adapters' K-extended q|k|v GEMM carries the RoPE "
+                                      "epilogue and cannot take the head norm")
         if self.embed_base is not None:
             raise RuntimeError("enable_lora after enable_embedding_training: the bucket is laid out [projector | adapters | embedding table]")
         self.lora = LoraParams(self.geo, cfg, self.proj, self.device)

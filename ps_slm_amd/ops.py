@@ -383,6 +383,16 @@ class HipOps:
         self._chk(self.lib.tasu_rope_bwd(_p(dqkv), _p(dk_part), _p(dv_part), _p(cos), _p(sin), B, S, H, G,
                                          self._stream()), "tasu_rope_bwd")
 
+    def qk_norm_rope_fwd(self, pre, wq, wk, cos, sin, out, rstd, M, H, G, eps):
+        """out = rope(w * bf16(pre * rstd)) per q / k head of the plain q|k|v projection ``pre`` (Qwen3: tasu_qk_norm_rope_fwd); v
+        heads copied; rstd [M, H+G] kept for qk_norm_bwd (None: no backward follows); out may be pre."""
+        self._chk(self.lib.tasu_qk_norm_rope_fwd(_p(pre), _p(wq), _p(wk), _p(cos), _p(sin), _p(out), _p(rstd), M, H, G, eps,
+                                                 self._stream()), "tasu_qk_norm_rope_fwd")
+
+    def qk_norm_bwd(self, dqkv, pre, wq, wk, rstd, M, H, G):
+        """In place on dqkv (behind the attention backward's RoPE backward): the q/k head norm's backward; v block untouched."""
+        self._chk(self.lib.tasu_qk_norm_bwd(_p(dqkv), _p(pre), _p(wq), _p(wk), _p(rstd), M, H, G, self._stream()), "tasu_qk_norm_bwd")
+
     def attn_fwd(self, qkv, vt, key_mask, out, lse, B, S, H, G, scale, causal):
         if self.attn_kernel["fwd"] != "policy":
             return self.attn_fwd_on(self.attn_kernel["fwd"], qkv, key_mask, out, lse, B, S, H, G, scale, causal)
@@ -720,6 +730,11 @@ class HipOps:
     def rope_append(self, qkv, cos, sin, kc, vc, pos, M, H, G, ctx):
         self._chk(self.lib.tasu_rope_append(_p(qkv), _p(cos), _p(sin), _p(kc), _p(vc), _p(pos), M, H, G, ctx, self._stream()),
                   "tasu_rope_append")
+
+    def qk_norm_rope_append(self, qkv, wq, wk, cos, sin, kc, vc, pos, M, H, G, ctx, eps):
+        """Qwen3 decode step: per-head q/k RMSNorm + RoPE in place on the plain q|k|v projection, k and v -> cache[row, pos[row]]."""
+        self._chk(self.lib.tasu_qk_norm_rope_append(_p(qkv), _p(wq), _p(wk), _p(cos), _p(sin), _p(kc), _p(vc), _p(pos), M, H, G, ctx, eps,
+                                                    self._stream()), "tasu_qk_norm_rope_append")
 
     def kv_index_init(self, index, B, nb, S, ctx):
         self._chk(self.lib.tasu_kv_index_init(_p(index), B, nb, S, ctx, self._stream()), "tasu_kv_index_init")

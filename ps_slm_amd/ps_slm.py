@@ -117,19 +117,36 @@ def setup_encoder_tokenizer(model_config, geo):
 def geometry_from_config(model_config, raw_features=False) -> Geometry:
     """HF config.json under llm_path when present; otherwise a named synthetic geometry
     (``llm_path = synthetic:qwen2.5-1.5b | synthetic:qwen2.5-7b | synthetic:mid | synthetic:mid-untied`` -- the last one is the mid
-    geometry with an lm_head of its own, the 7B's layout)."""
+    geometry with an lm_head of its own, the 7B's layout -- ``| synthetic:mid-qwen3 | synthetic:qwen3-1.7b``: Qwen3 decoders, a
+    per-head q/k RMSNorm and no q|k|v bias).  ``model_type == "qwen3"`` in the config.json selects the Qwen3 route; every other
+    value (or none) takes the Qwen2 route as before, except "qwen3_moe", which is refused."""
     path = str(model_config.get("llm_path", "") or "")
-    is_mid = path.lower() in ("synthetic:mid", "synthetic:mid-untied")    # the test geometry: encoder_dim / llm_dim overrides do not apply
+    is_mid = path.lower() in ("synthetic:mid", "synthetic:mid-untied", "synthetic:mid-qwen3")    # the test geometry: encoder_dim / llm_dim overrides do not apply
     cfg_file = os.path.join(path, "config.json")
     if os.path.isfile(cfg_file):
         c = json.load(open(cfg_file))
+        mt = str(c.get("model_type", "qwen2")).lower()
+        if mt == "qwen3_moe":
+            raise NotImplementedError("model_type 'qwen3_moe': the mixture-of-experts MLP is not built; the dense Qwen3 decoders "
+                                      "(model_type 'qwen3') are served, the MoE ones are a follow-up")
+        if mt == "qwen3" and c.get("use_sliding_window", False):
+            raise NotImplementedError("use_sliding_window=true: the attention kernels are full-causal only; sliding-window attention "
+                                      "is a follow-up")
         hd = c.get("head_dim", c["hidden_size"] // c["num_attention_heads"])
         if hd != 128:
             raise ValueError(f"head_dim {hd} is not supported by the gfx950 attention kernels (128 only)")
+        if mt == "qwen3" and c["num_attention_heads"] * 128 != c["hidden_size"]:
+            raise ValueError(f"model_type 'qwen3' with num_attention_heads * 128 = {c['num_attention_heads'] * 128} != hidden_size "
+                             f"{c['hidden_size']} (Qwen3-0.6B / 4B / 32B): q|k|v widths other than heads * 128 == hidden are a follow-up; "
+                             "Qwen3-1.7B / 8B / 14B are served")
         geo = Geometry(llm_vocab=c["vocab_size"], llm_dim=c["hidden_size"], llm_inter=c["intermediate_size"],
                        llm_layers=c["num_hidden_layers"], llm_heads=c["num_attention_heads"],
                        llm_kv_heads=c["num_key_value_heads"], rope_theta=float(c.get("rope_theta", 1e6)),
-                       rms_eps=float(c.get("rms_norm_eps", 1e-6)), tied=bool(c.get("tie_word_embeddings", True)))
+                       rms_eps=float(c.get("rms_norm_eps", 1e-6)), tied=bool(c.get("tie_word_embeddings", True)),
+                       qk_norm=mt == "qwen3", qkv_bias=mt != "qwen3")          # (any other model_type: the Qwen2 route, as before)
+        if mt == "qwen3" and c.get("attention_bias", False):
+            raise NotImplementedError("model_type 'qwen3' with attention_bias=true: the Qwen3 route's q|k|v projection is a plain GEMM "
+                                      "(no released Qwen3 checkpoint carries the bias)")
     elif path.startswith("synthetic:"):
         name = path.split(":", 1)[1].lower()
         if name in ("qwen2.5-1.5b", "1.5b"):
@@ -139,6 +156,11 @@ def geometry_from_config(model_config, raw_features=False) -> Geometry:
         elif name in ("mid", "mid-untied"):
             from ps_slm_amd.synthetic import MID_GEOMETRY
             geo = Geometry.from_dict(dict(MID_GEOMETRY, tied=name == "mid"))
+        elif name == "mid-qwen3":
+            from ps_slm_amd.synthetic import MID_GEOMETRY
+            geo = Geometry.from_dict(dict(MID_GEOMETRY, qk_norm=True, qkv_bias=False))
+        elif name in ("qwen3-1.7b", "qwen3-1p7b"):
+            geo = Geometry.qwen3_1p7b()
         else:
             raise ValueError(f"unknown synthetic geometry {name!r}")
     else:
@@ -293,6 +315,19 @@ def model_factory(train_config, model_config, **kwargs):
         raise NotImplementedError("ctc_posterior=false with the cross-attention projector: the reference's raw-feature branch "
                                   "(ps-slm.py:515-523) calls the projector with one argument, EncoderProjectorCTCCA needs two")
     geo = geometry_from_config(model_config, raw_features=raw)
+    if geo.qk_norm:
+        # Qwen3 (per-head q/k RMSNorm, csrc/qk_norm.hip): served on the bf16-autocast path with a frozen decoder; everything else is
+        # refused here, before any weight is built or any device work starts
+        if fp32_mode:
+            raise NotImplementedError("a Qwen3 decoder with train_config.use_fp16=false: the fp32 kernel family (generate(), evaluation "
+                                      "and the training step in fp32) has no q/k head norm yet -- set use_fp16=true; the fp32 family for "
+                                      "Qwen3 is the follow-up")
+        if use_peft:
+            raise NotImplementedError("a Qwen3 decoder with train_config.use_peft=true: the LoRA route's K-extended q|k|v GEMM carries "
+                                      "the RoPE epilogue and cannot take the head norm -- LoRA on Qwen3 is a follow-up; set use_peft=false")
+        if full_ft:
+            raise NotImplementedError("a Qwen3 decoder with train_config.freeze_llm=false: full fine-tuning needs the q_norm / k_norm "
+                                      "weights' gradients and their place in the trainable bucket -- a follow-up; set freeze_llm=true")
     geo.projector = projector
     geo.projector_ds_rate = int(model_config.get("encoder_projector_ds_rate", 1) or 1) if projector in ("linear", "cov1d-linear") else 1
     tokenizer = setup_tokenizer(train_config, model_config, geo, **kwargs)

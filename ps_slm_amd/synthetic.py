@@ -112,6 +112,25 @@ def decode_fixture_state_dict(geo: Geometry, seed: int, eos_boost=2.5):
     return sd
 
 
+def qwen3_state_dict(geo: Geometry, seed: int, decode_fixture=False, with_encoder=False, scale=0.05):
+    """A Qwen3 decoder's reference-named state dict: ``random_state_dict`` (or ``decode_fixture_state_dict``) with the three q|k|v
+    bias tensors of every layer removed and ``self_attn.q_norm.weight`` / ``k_norm.weight`` [128] added.  The norm weights are
+    1 + 0.5 N(0, 1), different for q and k and per layer (NOT HF's ones: a missing weight or a q / k swap must show), from a
+    generator of their own, so that the draws of ``random_state_dict`` -- every existing fixture's weights -- stay as they are."""
+    if decode_fixture:
+        sd = decode_fixture_state_dict(geo, seed)
+    else:
+        sd = random_state_dict(geo, seed, with_encoder=with_encoder, scale=scale)
+    g = torch.Generator().manual_seed(seed * 7919 + 3)
+    for l in range(geo.llm_layers):
+        p = f"llm.model.layers.{l}.self_attn."
+        for m in "qkv":
+            del sd[p + f"{m}_proj.bias"]
+        sd[p + "q_norm.weight"] = 1.0 + 0.5 * torch.randn(128, generator=g)
+        sd[p + "k_norm.weight"] = 1.0 + 0.5 * torch.randn(128, generator=g)
+    return sd
+
+
 def synthetic_text_batch(geo: Geometry, B, seed, prompt_len=25, n_audio=104, target_len=128, speech_pos=12,
                          feat_frames=500, noise=True, drop_prob=0.0, ragged=False):
     """One fixed-length (or ragged, for tests) text-only batch in the collator's schema

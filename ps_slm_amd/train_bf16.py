@@ -55,6 +55,10 @@ def forward_llm(model, st: StepState, compute_loss=True, need_backward=True, log
     b = SimpleNamespace(xs=xs, rstd=rstd, cos=cos, sin=sin, qkv=buf("qkv", (L, M, LDQ), bf), ao=buf("ao", (L, M, H * HD), bf),
                         lse=buf("lse", (L, B * H * Spad), f32), gu=buf("gu", (L, M, 2 * I), bf), xn=buf("xn_llm", (M, D), bf),
                         act=buf("act", (M, I), bf))
+    if geo.qk_norm and need_backward:
+        # Qwen3: the plain q|k|v projection of every layer (the head norm's backward reads it) and the heads' rstd; without a
+        # backward (eval forward, decode prefill) the norm runs in place on qkv[l] and keeps nothing
+        b.qkv_pre, b.qk_rstd = buf("qkv_pre", (L, M, LDQ), bf), buf("qk_rstd", (L, M, H + G), f32)
     lora, ft = model._lora_run, model.full_ft
     # full fine-tuning keeps the GEMM operands of every layer for the weight gradients (the normed inputs and the SwiGLU output;
     # the frozen step overwrites one buffer), and runs no compact tail: the last layer's MLP weights want all rows' operands in
@@ -71,6 +75,8 @@ def forward_llm(model, st: StepState, compute_loss=True, need_backward=True, log
     for l in range(L):
         layer_fwd(model, st, l, b, lora, ft if keep else None, drop, tail and l == L - 1)
     d.update(xs=xs, cos=cos, sin=sin, rstd=rstd, qkv=b.qkv, ao=b.ao, lse=b.lse, gu=b.gu)
+    if geo.qk_norm and need_backward:
+        d.update(qkv_pre=b.qkv_pre, qk_rstd=b.qk_rstd)
     if logits_rows == "none":                              # decode prefill: the caller projects the last rows only
         return
     if compute_loss and need_backward and not model.keep_logits:
@@ -106,7 +112,14 @@ def layer_fwd(model, st, l, b, lora=None, ft=None, drop=False, tail=False):
     a, x1, wq, K, ts = ad.group("qkv", l, M, xn1, w["wqkv"], D)
     ops.rmsnorm_fwd(x_in, w["ln1"], x1, b.rstd[2 * l], eps)
     ad.us(l, "qkv", ts, M, x1, drop, norm=(x_in, w["ln1"], b.rstd[2 * l]))
-    ops.gemm_qkv_rope(a, wq, w["bqkv"], b.qkv[l], b.cos, b.sin, M, H, G, K)
+    if geo.qk_norm:
+        # Qwen3: a plain NT GEMM, then the per-head q/k RMSNorm and the rotation in one row-wise launch (csrc/qk_norm.hip)
+        kept = hasattr(b, "qkv_pre")                       # (a backward follows; else in place: out == pre, no rstd -- the same bits)
+        pre = b.qkv_pre[l] if kept else b.qkv[l]
+        ops.gemm(a, wq, pre, M, (H + 2 * G) * HD, K)
+        ops.qk_norm_rope_fwd(pre, w["q_norm"], w["k_norm"], b.cos, b.sin, b.qkv[l], b.qk_rstd[l] if kept else None, M, H, G, eps)
+    else:
+        ops.gemm_qkv_rope(a, wq, w["bqkv"], b.qkv[l], b.cos, b.sin, M, H, G, K)
     ops.attn_fwd(b.qkv[l], None, d["key_mask"], b.ao[l], b.lse[l], B, S, H, G, HD ** -0.5, True)
     a, _, wo, K, ts = ad.group("o", l, M, b.ao[l], w["wo"], H * HD)
     if ts:
@@ -286,6 +299,8 @@ def layer_bwd(model, st, l, b, lora=None, ft=None, drop=False, mlp=True):
     # for Spad <= 256 (delta inside the kernel; dkp / dvp = one fp32 partial per query head), else the tiled kernels
     ops.attn_bwd_fused(d["qkv"][l], d["key_mask"], b.dao, d["ao"][l], d["lse"][l], b.delta, d["cos"], d["sin"], dqkv, b.dkp, b.dvp,
                        B, S, H, G, HD ** -0.5, True)
+    if geo.qk_norm:                                        # dqkv: gradient of the normed heads -> of the plain projection
+        ops.qk_norm_bwd(dqkv, d["qkv_pre"][l], w["q_norm"], w["k_norm"], d["qk_rstd"][l], M, H, G)
     if ft is not None:
         ft.wgrad(dqkv, d["ft_xn"][2 * l], "wqkv", l)
         ft.bias_wgrad(dqkv, "bqkv", l)                     # q|k|v bias: dqkv behind the RoPE backward

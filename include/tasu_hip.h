@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 25
+#define TASU_ABI_VERSION 26
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -788,6 +788,35 @@ int tasu_f32_gemm_swiglu(const float* A, int lda, const float* Wgu, int ldw, flo
 int tasu_f32_gemm_qkv_rope(const float* A, int lda, const float* Wqkv, int ldw, const float* bias, float* qkv, const float* cos_tab,
                            const float* sin_tab, int M, int H, int G, int K, float* kcache, float* vcache, const int32_t* slot, int ctx,
                            float* workspace, int64_t workspace_floats, void* stream);
+/* Qwen3's per-head q/k RMSNorm in the fp32 family (train_config.use_fp16 = false; csrc/qk_norm.hip, csrc/fp32.hip).  pre / out / dqkv /
+ * qkv: fp32 [M, (H+2G)*128]; wq / wk: fp32 [128], the layer's q_norm / k_norm weight; cos / sin: fp32 [M, 64] from tasu_rope_table;
+ * rstd: fp32 [M, H+G] (q heads, then k heads).  HF's Qwen3RMSNorm on fp32 tensors with no autocast, then apply_rotary_pos_emb:
+ * r = rsqrt(mean_128(pre^2) + eps), y = w * (pre * r) (two rounded products), out = y * cos + rotate_half(y) * sin with the two
+ * products rounded separately (tasu_f32_rope's rotation: one device function).  Nothing is rounded to bf16, no atomics, the same
+ * bits on every run.  Every pointer but rstd and slot is accessed in 16-byte vectors: a misaligned one is TASU_ERR_ARG, as are a
+ * NULL operand, H % G != 0, non-positive sizes and eps < 0, before any launch.
+ *   tasu_f32_qk_norm_rope:  out = rope(norm(pre)) on the q and k heads, v heads copied bit for bit; out == pre is allowed (any other
+ *           overlap is refused); rstd may be NULL when no backward follows.  kcache != NULL: the rotated k and the v of row m also
+ *           go to cache[m, slot[m]] (tasu_f32_rope's layout, cache [M, ctx, G*128]; a slot outside [0, ctx) writes nothing to the
+ *           cache) -- the forward and the decode step's append are ONE kernel: a key appended at decode time has the bits of the
+ *           same key out of a prefill.
+ *   tasu_f32_qk_norm_bwd:   in place on dqkv (g = the gradient w.r.t. the normed, weighted, UNROTATED head: what
+ *           tasu_f32_rope(inverse = 1) leaves): dpre = r (w g - xn mean_128(w g xn)), xn = pre r; v block untouched; dqkv == pre
+ *           is refused.
+ *   tasu_f32_gemm_qkv_norm_rope:  tasu_f32_gemm_qkv_rope with the head norm between the projection and the rotation (bias may be
+ *           NULL: Qwen3 has none).  Where the problem splits into K-range slabs, norm, rotation and append run in the launch that
+ *           sums them (ascending, f32_sum_slabs_qk_norm_rope_kernel); where it does not (the prompt pass), the GEMM and then
+ *           tasu_f32_qk_norm_rope in place.  Row-major and fragment-order weights as tasu_f32_gemm_qkv_rope takes them.  The
+ *           same bits as tasu_f32_gemm_nt followed by tasu_f32_qk_norm_rope, qkv and cache alike.                              */
+int tasu_f32_qk_norm_rope(const float* pre, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab, float* out,
+                          float* rstd, int M, int H, int G, float eps, float* kcache, float* vcache, const int32_t* slot, int ctx,
+                          void* stream);
+int tasu_f32_qk_norm_bwd(float* dqkv, const float* pre, const float* wq, const float* wk, const float* rstd, int M, int H, int G,
+                         void* stream);
+int tasu_f32_gemm_qkv_norm_rope(const float* A, int lda, const float* Wqkv, int ldw, const float* bias, float* qkv, const float* wq,
+                                const float* wk, const float* cos_tab, const float* sin_tab, int M, int H, int G, int K, float eps,
+                                float* kcache, float* vcache, const int32_t* slot, int ctx, float* workspace, int64_t workspace_floats,
+                                void* stream);
 /* y = w * (x * rsqrt(mean(x^2) + eps)) per row of x [M, D] */
 int tasu_f32_rmsnorm(const float* x, const float* w, float* y, int M, int D, float eps, void* stream);
 /* q and k heads of qkv [M, (H+2G)*128] rotated in place (tables [M, 64] of tasu_rope_table; x*cos + rotate_half(x)*sin with the two

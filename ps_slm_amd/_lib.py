@@ -157,6 +157,9 @@ PROTOTYPES.update({
     "tasu_f32_gemm_swiglu": [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, i64, vp],
     "tasu_f32_gemm_qkv_rope": [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, i64, vp],
     "tasu_f32_rope": [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp],
+    "tasu_f32_qk_norm_rope": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp],
+    "tasu_f32_qk_norm_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "tasu_f32_gemm_qkv_norm_rope": [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, i64, vp],
     "tasu_f32_kv_fill": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "tasu_f32_attn_prefill": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "tasu_f32_fsmn": [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp],
@@ -193,7 +196,7 @@ PROTOTYPES.update({
     "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm_dispatch.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <utility>
 #include "common.h"
+#include "f32_qk_head.h"
 #include "../../include/tasu_hip.h"
 
 namespace tasu_f32 {
@@ -16,16 +17,7 @@ constexpr int BM = 64, BN = 64, BK = 32, LDS_LD = BK + 4;     // row pitch 36 fl
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float silu_exact(float x) { return x / (1.f + expf(-x)); }
-// x * cos + rotate_half(x) * sin with the two products and the sum rounded separately, like torch eager (apply_rotary_pos_emb):
-// -ffp-contract=fast would otherwise fuse one product into the sum, and not the same one at every call site
-__device__ __forceinline__ void rope_pair_eager(float x1, float x2, float c, float s, float& y1, float& y2) {
-  // (every product passes through an empty asm before it is used: a pragma `fp contract(off)` here did not survive inlining into
-  // f32_sum_slabs_rope_kernel, which came out with a v_pk_fma_f32 where f32_rope_kernel has mul + add)
-  float a1 = x1 * c, b1 = x2 * s, a2 = x2 * c, b2 = x1 * s;
-  asm volatile("" : "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2));
-  y1 = a1 - b1;
-  y2 = a2 + b2;
-}
+// (rope_pair_eager -- apply_rotary_pos_emb with separately rounded products -- and Qwen3's head norm: f32_qk_head.h)
 __device__ __forceinline__ float act_f(float v, int act) { return act == 1 ? silu_exact(v) : (act == 2 ? fmaxf(v, 0.f) : v); }
 
 // C[m, n] (+)= sum_k A[m, k] W[n, k] over the K range of blockIdx.z.  ksplit == 1: C = [resid +] act(acc + bias).
@@ -379,6 +371,39 @@ __global__ __launch_bounds__(256) void f32_sum_slabs_rope_kernel(const float* __
     dst[d] = y1;
     dst[d + 64] = y2;
   }
+}
+
+// f32_sum_slabs_rope_kernel for a Qwen3 decoder: qkv = sum [+ bias], the q / k heads normed per head and rotated, k / v appended
+// to the cache.  f32_qk_head.h's thread map (32 lanes per (row, head), one 16-byte vector per lane) and its device function: the
+// bits of f32_sum_slabs_kernel followed by f32_qk_norm_rope_kernel (csrc/qk_norm.hip).  A slot outside [0, ctx) writes no cache.
+__global__ __launch_bounds__(256) void f32_sum_slabs_qk_norm_rope_kernel(const float* __restrict__ slabs, int ksplit, float* __restrict__ qkv,
+                                                                         const float* __restrict__ bias, const float* __restrict__ wq,
+                                                                         const float* __restrict__ wk, const float* __restrict__ ct,
+                                                                         const float* __restrict__ st, int M, int H, int G, float eps,
+                                                                         float* __restrict__ kc, float* __restrict__ vc,
+                                                                         const int32_t* __restrict__ slot, int ctx) {
+  const int NH = H + 2 * G, sub = threadIdx.x & (QK_LANES - 1);
+  const long long unit = (long long)blockIdx.x * QK_HEADS_PER_BLOCK + threadIdx.x / QK_LANES;
+  const bool live = unit < (long long)M * NH;
+  const int row = live ? (int)(unit / NH) : 0, hh = live ? (int)(unit % NH) : 0;      // (a spare group computes row 0, head 0 and stores nothing)
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 4, stride = (size_t)M * NH * HD;
+  f32x4 x = *(const f32x4*)(slabs + off);
+  for (int s = 1; s < ksplit; ++s) x += *(const f32x4*)(slabs + s * stride + off);   // (ascending, like f32_sum_slabs_kernel)
+  if (bias) x += *(const f32x4*)(bias + hh * HD + sub * 4);
+  const int at = kc ? slot[row] : -1;
+  const bool slot_ok = live && at >= 0 && at < ctx;
+  const size_t cell = ((size_t)row * ctx + (slot_ok ? at : 0)) * ((size_t)G * HD) + sub * 4;
+  if (hh >= H + G) {                                       // a v head: the projection's bits (whole 32-lane groups leave)
+    if (live) *(f32x4*)(qkv + off) = x;
+    if (slot_ok) *(f32x4*)(vc + cell + (size_t)(hh - H - G) * HD) = x;
+    return;
+  }
+  const int p = (sub & 15) * 4;
+  float r;
+  const f32x4 y = f32_qk_head_fwd(x, (hh < H ? wq : wk) + sub * 4, ct + (size_t)row * 64 + p, st + (size_t)row * 64 + p, eps, sub, r);
+  if (!live) return;
+  *(f32x4*)(qkv + off) = y;
+  if (hh >= H && slot_ok) *(f32x4*)(kc + cell + (size_t)(hh - H) * HD) = y;
 }
 
 // Qwen2RMSNorm in fp32 (modeling_qwen2.py:41-48): y = w * (x * rsqrt(mean(x^2) + eps)); one 1024-thread block per row
@@ -1044,6 +1069,35 @@ extern "C" int tasu_f32_gemm_qkv_rope(const float* A, int lda, const float* Wqkv
   if (rc) return rc;
   TASU_LAUNCH(f32_sum_slabs_rope_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, workspace, ksplit, qkv, bias,
               cos_tab, sin_tab, M, H, G, kcache, vcache, slot, ctx);
+  return TASU_OK;
+}
+
+// tasu_f32_gemm_qkv_rope for a Qwen3 decoder: qkv = A Wqkv^T [+ bias], per-head RMSNorm (wq / wk) and rotation of the q / k heads,
+// k / v appended to the cache -- in the launch that sums the K-range slabs; unsplit problems (the prompt pass): the GEMM, then
+// tasu_f32_qk_norm_rope in place.  Every argument is checked here, before the GEMM is launched.
+extern "C" int tasu_f32_gemm_qkv_norm_rope(const float* A, int lda, const float* Wqkv, int ldw, const float* bias, float* qkv, const float* wq,
+                                           const float* wk, const float* cos_tab, const float* sin_tab, int M, int H, int G, int K, float eps,
+                                           float* kcache, float* vcache, const int32_t* slot, int ctx, float* workspace,
+                                           int64_t workspace_floats, void* stream) {
+  const int N = (H + 2 * G) * HD;
+  if (H <= 0 || G <= 0 || H % G || !f32_gemm_args_ok(A, lda, Wqkv, ldw, qkv, N, M, N, K) || !wq || !wk || !cos_tab || !sin_tab || !(eps >= 0.f) ||
+      (long long)M * (H + 2 * G) > 0x7fffffffLL / QK_LANES)
+    return TASU_ERR_ARG;
+  if (kcache && (!vcache || !slot || ctx <= 0)) return TASU_ERR_ARG;
+  if (((uintptr_t)qkv | (uintptr_t)wq | (uintptr_t)wk | (uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)bias | (uintptr_t)kcache |
+       (uintptr_t)vcache | (uintptr_t)workspace) & 15)
+    return TASU_ERR_ARG;                                  // (16-byte vectors; NULL is aligned)
+  const int ksplit = f32_ksplit(M, N, K, workspace, workspace_floats);
+  if (ksplit == 1) {
+    const int rc = f32_gemm_launch(A, lda, Wqkv, ldw, qkv, N, bias, nullptr, M, N, K, 0, 1, workspace, workspace_floats, (hipStream_t)stream);
+    if (rc) return rc;
+    return tasu_f32_qk_norm_rope(qkv, wq, wk, cos_tab, sin_tab, qkv, nullptr, M, H, G, eps, kcache, vcache, slot, ctx, stream);
+  }
+  const int rc = f32_gemm_launch(A, lda, Wqkv, ldw, workspace, N, nullptr, nullptr, M, N, K, 0, ksplit, workspace, workspace_floats, (hipStream_t)stream);
+  if (rc) return rc;
+  const long long units = (long long)M * (H + 2 * G);
+  TASU_LAUNCH(f32_sum_slabs_qk_norm_rope_kernel, dim3((unsigned)((units + QK_HEADS_PER_BLOCK - 1) / QK_HEADS_PER_BLOCK)), dim3(256), 0,
+              (hipStream_t)stream, workspace, ksplit, qkv, bias, wq, wk, cos_tab, sin_tab, M, H, G, eps, kcache, vcache, slot, ctx);
   return TASU_OK;
 }
 

@@ -16,7 +16,15 @@
 // share qk_head_fwd: a key appended at decode time has the bits of the same key out of a prefill.
 //
 // Cost, DERIVED (not measured here): one read and one write of [M, (H+2G)*128] bf16 per launch (the v block only when out != pre).
+//
+// The fp32 family (train_config.use_fp16 = false: HF's Qwen3RMSNorm on fp32 tensors with no autocast, nothing rounded to bf16):
+//   tasu_f32_qk_norm_rope      out = rope(w * (pre * r)), v heads copied bit for bit, r kept on request; with a cache the rotated
+//                              k and the v of row m also go to cache[m, slot[m]] (tasu_f32_rope's layout) -- forward and append
+//   tasu_f32_qk_norm_bwd       dpre = r (w g - xn mean_128(w g xn)),  xn = pre r, in place on dqkv behind tasu_f32_rope(inverse = 1)
+// Thread map and device function: f32_qk_head.h (32 lanes per (row, head), one 16-byte vector per lane), shared with
+// f32_sum_slabs_qk_norm_rope_kernel of csrc/fp32.hip.  Cost, DERIVED: one read and one write of [M, (H+2G)*128] fp32.
 #include "common.h"
+#include "f32_qk_head.h"
 #include "../../include/tasu_hip.h"
 
 namespace {
@@ -135,11 +143,73 @@ __global__ __launch_bounds__(256) void qk_norm_rope_append_kernel(bf16* __restri
   if (hh >= H && slot_ok) *(bf16x8*)(kc + slot + (size_t)(hh - H) * HD + sub * 8) = y;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- fp32 family
+using tasu_f32::QK_HEADS_PER_BLOCK;
+using tasu_f32::QK_LANES;
+
+__global__ __launch_bounds__(256) void f32_qk_norm_rope_kernel(const float* pre, const float* __restrict__ wq, const float* __restrict__ wk,
+                                                               const float* __restrict__ ct, const float* __restrict__ st, float* out,
+                                                               float* __restrict__ rstd, int M, int H, int G, float eps,
+                                                               float* __restrict__ kc, float* __restrict__ vc,
+                                                               const int32_t* __restrict__ slot, int ctx) {
+  // (pre / out carry no __restrict__: out == pre is allowed; a lane reads its vector before it stores to the same address)
+  const int NH = H + 2 * G, sub = threadIdx.x & (QK_LANES - 1);
+  const long long unit = (long long)blockIdx.x * QK_HEADS_PER_BLOCK + threadIdx.x / QK_LANES;
+  const bool live = unit < (long long)M * NH;
+  const int row = live ? (int)(unit / NH) : 0, hh = live ? (int)(unit % NH) : 0;      // (a spare group computes row 0, head 0 and stores nothing)
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 4;
+  const f32x4 x = *(const f32x4*)(pre + off);
+  const int at = kc ? slot[row] : -1;
+  const bool slot_ok = live && at >= 0 && at < ctx;        // a slot outside the cache writes nothing there
+  const size_t cell = ((size_t)row * ctx + (slot_ok ? at : 0)) * ((size_t)G * HD) + sub * 4;
+  if (hh >= H + G) {                                       // a v head: the projection's bits (whole 32-lane groups leave)
+    if (live && out != pre) *(f32x4*)(out + off) = x;
+    if (slot_ok) *(f32x4*)(vc + cell + (size_t)(hh - H - G) * HD) = x;
+    return;
+  }
+  const int p = (sub & 15) * 4;
+  float r;
+  const f32x4 y = tasu_f32::f32_qk_head_fwd(x, (hh < H ? wq : wk) + sub * 4, ct + (size_t)row * 64 + p, st + (size_t)row * 64 + p, eps, sub, r);
+  if (!live) return;
+  *(f32x4*)(out + off) = y;
+  if (rstd && sub == 0) rstd[(size_t)row * (H + G) + hh] = r;
+  if (hh >= H && slot_ok) *(f32x4*)(kc + cell + (size_t)(hh - H) * HD) = y;
+}
+
+__global__ __launch_bounds__(256) void f32_qk_norm_bwd_kernel(float* __restrict__ dqkv, const float* __restrict__ pre,
+                                                              const float* __restrict__ wq, const float* __restrict__ wk,
+                                                              const float* __restrict__ rstd, int M, int H, int G) {
+  const int NH = H + 2 * G, NQK = H + G, sub = threadIdx.x & (QK_LANES - 1);
+  const long long unit = (long long)blockIdx.x * QK_HEADS_PER_BLOCK + threadIdx.x / QK_LANES;      // over the q and k heads only
+  const bool live = unit < (long long)M * NQK;
+  const int row = live ? (int)(unit / NQK) : 0, hh = live ? (int)(unit % NQK) : 0;
+  const size_t off = ((size_t)row * NH + hh) * HD + sub * 4;
+  const f32x4 x = *(const f32x4*)(pre + off), g = *(const f32x4*)(dqkv + off);
+  const f32x4 w = *(const f32x4*)((hh < H ? wq : wk) + sub * 4);
+  const float r = rstd[(size_t)row * NQK + hh];
+  float wg[4], xn[4], dot = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    wg[j] = w[j] * g[j];
+    xn[j] = x[j] * r;
+    dot = __builtin_fmaf(wg[j], xn[j], dot);
+  }
+  const float mean = tasu_f32::group32_sum(dot) * (1.0f / HD);
+  f32x4 d;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d[j] = r * (wg[j] - xn[j] * mean);
+  if (live) *(f32x4*)(dqkv + off) = d;
+}
+
 inline bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 inline bool shape_ok(int M, int H, int G) {
   return M > 0 && H > 0 && G > 0 && H % G == 0 && (long long)M * (H + 2 * G) <= 0x7fffffffLL / 16;
 }
 inline unsigned blocks_for(long long units) { return (unsigned)((units + 15) / 16); }
+inline bool f32_shape_ok(int M, int H, int G) {
+  return M > 0 && H > 0 && G > 0 && H % G == 0 && (long long)M * (H + 2 * G) <= 0x7fffffffLL / QK_LANES;
+}
+inline unsigned f32_blocks_for(long long units) { return (unsigned)((units + QK_HEADS_PER_BLOCK - 1) / QK_HEADS_PER_BLOCK); }
 
 }  // namespace
 
@@ -177,5 +247,31 @@ extern "C" int tasu_qk_norm_rope_append(void* qkv, const float* wq, const float*
     return TASU_ERR_ARG;
   TASU_LAUNCH(qk_norm_rope_append_kernel, dim3(blocks_for((long long)M * (H + 2 * G))), dim3(256), 0, (hipStream_t)stream,
               (bf16*)qkv, wq, wk, cos_tab, sin_tab, (bf16*)kcache, (bf16*)vcache, pos, M, H, G, ctx, eps);
+  return TASU_OK;
+}
+
+extern "C" int tasu_f32_qk_norm_rope(const float* pre, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab,
+                                     float* out, float* rstd, int M, int H, int G, float eps, float* kcache, float* vcache,
+                                     const int32_t* slot, int ctx, void* stream) {
+  if (!pre || !wq || !wk || !cos_tab || !sin_tab || !out || !f32_shape_ok(M, H, G) || !(eps >= 0.f)) return TASU_ERR_ARG;
+  if (misaligned(pre) || misaligned(wq) || misaligned(wk) || misaligned(cos_tab) || misaligned(sin_tab) || misaligned(out))
+    return TASU_ERR_ARG;
+  if (kcache && (!vcache || !slot || ctx <= 0 || misaligned(kcache) || misaligned(vcache))) return TASU_ERR_ARG;
+  if (out != pre) {                                        // the same buffer, or two that do not overlap
+    const size_t bytes = (size_t)M * (H + 2 * G) * HD * sizeof(float);
+    const uintptr_t a = (uintptr_t)pre, b = (uintptr_t)out;
+    if (a < b + bytes && b < a + bytes) return TASU_ERR_ARG;
+  }
+  TASU_LAUNCH(f32_qk_norm_rope_kernel, dim3(f32_blocks_for((long long)M * (H + 2 * G))), dim3(256), 0, (hipStream_t)stream, pre, wq, wk,
+              cos_tab, sin_tab, out, rstd, M, H, G, eps, kcache, vcache, slot, ctx);
+  return TASU_OK;
+}
+
+extern "C" int tasu_f32_qk_norm_bwd(float* dqkv, const float* pre, const float* wq, const float* wk, const float* rstd, int M, int H,
+                                    int G, void* stream) {
+  if (!dqkv || !pre || !wq || !wk || !rstd || dqkv == pre || !f32_shape_ok(M, H, G)) return TASU_ERR_ARG;
+  if (misaligned(dqkv) || misaligned(pre) || misaligned(wq) || misaligned(wk)) return TASU_ERR_ARG;
+  TASU_LAUNCH(f32_qk_norm_bwd_kernel, dim3(f32_blocks_for((long long)M * (H + G))), dim3(256), 0, (hipStream_t)stream, dqkv, pre, wq, wk,
+              rstd, M, H, G);
   return TASU_OK;
 }

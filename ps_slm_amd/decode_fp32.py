@@ -16,6 +16,10 @@ softmax and PSD in fp32 as well (ps_slm_amd/encoder.py: encoder_posterior_fp32; 
 ``arith == "fp32"`` and no labels are given).  Pinned by exact token equality with the REAL reference on 24 unfiltered random cases,
 the 17 rounding-stable ones and the text + audio fixture (tests/test_gpu_model.py).
 
+A Qwen3 decoder (``geo.qk_norm``: an RMSNorm over each 128-wide q and k head between the projection and the rotation, no q|k|v bias)
+takes ``tasu_f32_gemm_qkv_norm_rope`` where a Qwen2 layer takes ``tasu_f32_gemm_qkv_rope`` -- HF's Qwen3RMSNorm on fp32 tensors, in the
+launch that sums the projection's K-range slabs (csrc/qk_norm.hip, csrc/fp32.hip) -- and is otherwise the same path.
+
 HBM-bound like the bf16 step, on twice the bytes: 6.2 GB of fp32 weights per generated position at Qwen2.5-1.5B.
 """
 import numpy as np
@@ -130,18 +134,30 @@ def weights_f32(model):
 
 
 def _layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, cache=None, ctx=0, frag=None,
-                keep_gu=False):
+                keep_gu=False, keep_qk=None):
     """One decoder layer; in: xn = RMSNorm(x_in, ln1[l]); out: x_mid = x_in + attention, x_out = x_mid + MLP, xn = the NEXT norm of
     x_out (ln1[l + 1], or the final norm).  Decode and eval pass one buffer three times; the training step passes its kept slices.
     Every projection carries the row-wise kernel behind it in the launch that sums its K-range slabs (tasu_f32_gemm_qkv_rope,
     _resid_rmsnorm, _swiglu): 9 launches per layer at <= 64 beam rows instead of 13.  ``keep_gu``: gate|up is kept in ``gu`` for
-    the backward, so it runs as its own GEMM and SwiGLU instead of the fused finisher."""
+    the backward, so it runs as its own GEMM and SwiGLU instead of the fused finisher.  A qk_norm geometry (Qwen3) takes
+    tasu_f32_gemm_qkv_norm_rope in the place of tasu_f32_gemm_qkv_rope -- the per-head q/k RMSNorm between the projection and the
+    rotation, in the same launch; ``keep_qk = (pre, rstd)`` (the training step): the plain projection and the heads' rstd are kept
+    for the backward, so the GEMM and the row kernel run as two launches."""
     ops, geo, llm = model.ops, model.geo, model.llm
     D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
     f, w = weights_f32(model)["layers"][l], llm.layers[l]
     next_norm = llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm
     kc_l, vc_l, slot = cache if cache is not None else (None, None, None)
-    ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, cos_t, sin_t, rows, H, G, D, ws, kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
+    if not geo.qk_norm:
+        ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, cos_t, sin_t, rows, H, G, D, ws, kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
+    elif keep_qk is None:
+        ops.f32_gemm_qkv_norm_rope(xn, f["wqkv"], None, qkv, f["q_norm"], f["k_norm"], cos_t, sin_t, rows, H, G, D, geo.rms_eps, ws,
+                                   kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
+    else:
+        pre, rstd = keep_qk
+        ops.f32_gemm(xn, f["wqkv"], pre, rows, (H + 2 * G) * HD, D, ws=ws)
+        ops.f32_qk_norm_rope(pre, f["q_norm"], f["k_norm"], cos_t, sin_t, qkv, rstd, rows, H, G, geo.rms_eps, kc=kc_l, vc=vc_l,
+                             slot=slot, ctx=ctx)
     attend(l, qkv, ao)
     ops.f32_gemm_resid_rmsnorm(ao, f["wo"], x_mid, w["ln2"], xn, rows, D, H * HD, geo.rms_eps, ws, resid=x_in)
     wgu, wd = (f["wgu"], f["wd"]) if frag is None else (ops.f32_weight(frag["layers"][l]["wgu"], rows, ws), ops.f32_weight(frag["layers"][l]["wd"], rows, ws))
@@ -166,7 +182,8 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
     QUERY rows hold garbage nobody reads).  ``on_layer(l, qkv)``: called with the layer's rotated q|k|v (generate() fills its cache
     there).  ``keep`` (a dict: the training step): every layer's activations go to stacked buffers -- layer l reads xs[2l] and
     writes xs[2l + 1] and xs[2l + 2] -- gate|up runs unfused, and ``keep`` receives what backward_fp32 reads (xs, qkvs, aos, gus,
-    cos, sin, kstart and the projector's, project_fp32).  Returns (xn0 = the final-normed hidden states [B * S, D], valid, left)."""
+    cos, sin, kstart and the projector's, project_fp32; on a qk_norm geometry also qkv_pres and qk_rstds, the plain projections and
+    the heads' rstd).  Returns (xn0 = the final-normed hidden states [B * S, D], valid, left)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     B, S = st.B, st.S
@@ -194,6 +211,8 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
     else:
         xs, qkvs = buf("f32t_xs", (2 * L + 1, M0, D), f32), buf("f32t_qkv", (L, M0, LDQ), f32)
         aos, gus = buf("f32t_ao", (L, M0, H * HD), f32), buf("f32t_gu", (L, M0, 2 * I), f32)
+    # Qwen3's training step: every layer's plain projection and head rstd, what tasu_f32_qk_norm_bwd reads
+    pres, rstds = (buf("f32t_qkv_pre", (L, M0, LDQ), f32), buf("f32t_qk_rstd", (L, M0, H + G), f32)) if keep is not None and geo.qk_norm else (None, None)
     ops.f32_embed_merge(llm.embed, y2, d["kind"], d["idx"], xs[0], M0, D)
     cos0, sin0 = buf("f32_cos0", (M0, HD // 2), f32), buf("f32_sin0", (M0, HD // 2), f32)
     ops.rope_table(d["pos"], cos0, sin0, HD, geo.rope_theta)
@@ -209,10 +228,13 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
         from .train_fp32 import lora_layer_fp32 as layer
     ops.f32_rmsnorm(xs[0], llm.layers[0]["ln1"], xn0, M0, D, geo.rms_eps)
     for l in range(L):
+        kw = dict(keep_qk=(pres[l], rstds[l])) if pres is not None else {}
         layer(model, l, xs[2 * l], xs[2 * l + 1], xs[2 * l + 2], xn0, qkvs[l], aos[l], gus[l], act0, M0, cos0, sin0, attend_prompt,
-                    ws, keep_gu=keep is not None)
+                    ws, keep_gu=keep is not None, **kw)
     if keep is not None:
         keep.update(xs=xs, qkvs=qkvs, aos=aos, gus=gus, cos=cos0, sin=sin0, kstart=kstart_b)
+        if pres is not None:
+            keep.update(qkv_pres=pres, qk_rstds=rstds)
     return xn0, valid, left
 
 

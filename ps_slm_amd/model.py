@@ -236,6 +236,17 @@ class ProjectorParams:
         ops.transpose(self.view(self.pb, self.n_w2), self.w2b_t, self.Do, self.Hb, self.Do, self.Hb)
 
 
+F32_QK_NORM_OPS = ("f32_qk_norm_rope", "f32_qk_norm_bwd", "f32_gemm_qkv_norm_rope")
+
+
+def f32_qk_norm_missing(ops):
+    """The fp32 head-norm operators (csrc/qk_norm.hip, csrc/fp32.hip) that the CLASS of an operator set lacks: a capability probe
+    that touches no instance attribute, so it is no device work (``ops`` None: HipOps, which has them)."""
+    if ops is None:
+        return ()
+    return tuple(n for n in F32_QK_NORM_OPS if not callable(getattr(type(ops), n, None)))
+
+
 class LLMWeights:
     """Frozen Qwen2 weights, bf16, fused and doubly laid out (see module docstring)."""
 
@@ -253,6 +264,9 @@ class LLMWeights:
         # fused weights next to the bf16 ones, {"layers": [{wqkv, bqkv, wo, wgu, wd}], "head"}; set keep_f32 BEFORE loading
         self.keep_f32 = False
         self.f32 = None
+        # a qk_norm (Qwen3) decoder keeps fp32 copies only for an operator set that has the fp32 head-norm operators
+        # (f32_qk_norm_missing of its CLASS is empty: TasuModel sets this)
+        self.f32_qk_norm_ok = False
 
     def _drop_weights(self):
         """Before a reload: remember which registered decode copies die with the old tensors."""
@@ -274,8 +288,9 @@ class LLMWeights:
         """bq / bk / bv None: a decoder without q|k|v bias (Qwen3; a zero bias is kept for the consumers that read one).
         q_norm / k_norm: Qwen3's per-head norm weights [128], kept in fp32."""
         dev = self.device
-        if self.geo.qk_norm and self.keep_f32:
-            raise NotImplementedError("a qk_norm (Qwen3) decoder in fp32 arithmetic: the fp32 kernel family has no q/k head norm")
+        if self.geo.qk_norm and self.keep_f32 and not self.f32_qk_norm_ok:
+            raise NotImplementedError("a qk_norm (Qwen3) decoder in fp32 arithmetic: this operator set has no fp32 q/k head norm "
+                                      f"({', '.join(F32_QK_NORM_OPS)})")
         if bq is None:
             bq, bk, bv = (torch.zeros(w.shape[0], dtype=w.dtype, device=w.device) for w in (wq, wk, wv))
         wqkv, wqkv_t = self._pair(torch.cat([wq, wk, wv], 0), dev)
@@ -296,6 +311,8 @@ class LLMWeights:
             c = lambda t: t.to(dev, torch.float32).contiguous()
             self.f32["layers"].append(dict(wqkv=c(torch.cat([wq, wk, wv], 0)), bqkv=c(torch.cat([bq, bk, bv], 0)), wo=c(wo),
                                            wgu=c(torch.cat([wg, wu], 0)), wd=c(wd)))
+            if self.geo.qk_norm:                           # the head norms: the fp32 tensors of the bf16 layer dict, not copies
+                self.f32["layers"][-1].update(q_norm=self.layers[-1]["q_norm"], k_norm=self.layers[-1]["k_norm"])
 
     def set_embed(self, embed, head, norm):
         geo, dev = self.geo, self.device
@@ -463,6 +480,7 @@ class TasuModel:
     def __init__(self, geo: Geometry, ops, device, keep_logits=True):
         self.geo, self.ops, self.device = geo, ops, torch.device(device)
         self.llm = LLMWeights(geo, self.device)
+        self.llm.f32_qk_norm_ok = not f32_qk_norm_missing(ops)
         self.proj = ProjectorParams(geo, self.device)
         self.encoder = None            # ps_slm_amd.encoder.EncoderWeights (audio path)
         self.keep_logits = keep_logits

@@ -867,6 +867,25 @@ class HipOps:
                                                   K, _p(kc), _p(vc), _p(slot), ctx, _p(ws), ws.numel() if ws is not None else 0,
                                                   self._stream()), "tasu_f32_gemm_qkv_rope")
 
+    def f32_gemm_qkv_norm_rope(self, a, wqkv, bias, qkv, wq, wk, cos, sin, M, H, G, K, eps, ws, kc=None, vc=None, slot=None, ctx=0):
+        """f32_gemm_qkv_rope for a Qwen3 decoder: the per-head q/k RMSNorm (wq / wk [128]) between the projection and the rotation,
+        in the launch that sums the K-range slabs (tasu_f32_gemm_qkv_norm_rope); ``bias`` may be None."""
+        self._chk(self.lib.tasu_f32_gemm_qkv_norm_rope(_p(a), a.stride(0), *_wl(wqkv), _p(bias), _p(qkv), _p(wq), _p(wk), _p(cos), _p(sin),
+                                                       M, H, G, K, eps, _p(kc), _p(vc), _p(slot), ctx, _p(ws),
+                                                       ws.numel() if ws is not None else 0, self._stream()), "tasu_f32_gemm_qkv_norm_rope")
+
+    def f32_qk_norm_rope(self, pre, wq, wk, cos, sin, out, rstd, M, H, G, eps, kc=None, vc=None, slot=None, ctx=0):
+        """out = rope(w * (pre * rstd)) per q / k head of the plain fp32 q|k|v projection ``pre`` (Qwen3 in fp32 arithmetic:
+        tasu_f32_qk_norm_rope); v heads copied; rstd [M, H+G] kept for f32_qk_norm_bwd (None: no backward follows); out may be
+        pre; with a cache the rotated k and v also go to cache[m, slot[m]]."""
+        self._chk(self.lib.tasu_f32_qk_norm_rope(_p(pre), _p(wq), _p(wk), _p(cos), _p(sin), _p(out), _p(rstd), M, H, G, eps, _p(kc), _p(vc),
+                                                 _p(slot), ctx, self._stream()), "tasu_f32_qk_norm_rope")
+
+    def f32_qk_norm_bwd(self, dqkv, pre, wq, wk, rstd, M, H, G):
+        """dqkv (the gradient of the normed heads, behind f32_rope(inverse=True)) -> the gradient of the plain projection, in place."""
+        self._chk(self.lib.tasu_f32_qk_norm_bwd(_p(dqkv), _p(pre), _p(wq), _p(wk), _p(rstd), M, H, G, self._stream()),
+                  "tasu_f32_qk_norm_bwd")
+
     def f32_rmsnorm(self, x, w, y, M, D, eps):
         self._chk(self.lib.tasu_f32_rmsnorm(_p(x), _p(w), _p(y), M, D, eps, self._stream()), "tasu_f32_rmsnorm")
 

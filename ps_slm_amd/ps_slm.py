@@ -214,7 +214,11 @@ def load_hf_llm_state_dict(path):
 
 
 def model_factory(train_config, model_config, **kwargs):
-    """Same contract as Multitask/model/ps-slm.py:130-181: returns (model, tokenizer)."""
+    """Same contract as Multitask/model/ps-slm.py:130-181: returns (model, tokenizer).  train_config.use_fp16 selects the arithmetic
+    for Qwen2 and Qwen3 decoders alike: true -> the bf16-autocast path, false (the reference's shipped scripts) -> the fp32 kernels
+    for generate(), evaluation and, where train_fp32.py serves the recipe, the training step.  A Qwen3 decoder (per-head q/k
+    RMSNorm) in fp32 needs an operator set whose class has f32_qk_norm_rope / f32_qk_norm_bwd / f32_gemm_qkv_norm_rope (HipOps
+    has them); with use_peft=true or freeze_llm=false it is refused on either path."""
     projector = model_config.get("encoder_projector", "linear-silu")
     if projector == "q-former":
         # FINDING: the reference cannot run its q-former either.  EncoderProjectorQFormer.forward(x, atts) (projector.py:91-100)
@@ -316,12 +320,16 @@ def model_factory(train_config, model_config, **kwargs):
                                   "(ps-slm.py:515-523) calls the projector with one argument, EncoderProjectorCTCCA needs two")
     geo = geometry_from_config(model_config, raw_features=raw)
     if geo.qk_norm:
-        # Qwen3 (per-head q/k RMSNorm, csrc/qk_norm.hip): served on the bf16-autocast path with a frozen decoder; everything else is
-        # refused here, before any weight is built or any device work starts
+        # Qwen3 (per-head q/k RMSNorm, csrc/qk_norm.hip): served with a frozen decoder on the bf16-autocast path and, for an operator
+        # set whose class has the fp32 head-norm operators (HipOps does), on the fp32 path; everything else is refused here, before
+        # any weight is built or any device work starts (the probe reads the operator set's CLASS, never the instance)
         if fp32_mode:
-            raise NotImplementedError("a Qwen3 decoder with train_config.use_fp16=false: the fp32 kernel family (generate(), evaluation "
-                                      "and the training step in fp32) has no q/k head norm yet -- set use_fp16=true; the fp32 family for "
-                                      "Qwen3 is the follow-up")
+            from ps_slm_amd.model import f32_qk_norm_missing
+            missing = f32_qk_norm_missing(kwargs.get("ops", None))
+            if missing:
+                raise NotImplementedError("a Qwen3 decoder with train_config.use_fp16=false: this operator set has no fp32 q/k head norm "
+                                          f"(missing: {', '.join(missing)}) for generate(), evaluation and the training step in fp32 -- "
+                                          "set use_fp16=true, or use the HIP operator set")
         if use_peft:
             raise NotImplementedError("a Qwen3 decoder with train_config.use_peft=true: the LoRA route's K-extended q|k|v GEMM carries "
                                       "the RoPE epilogue and cannot take the head norm -- LoRA on Qwen3 is a follow-up; set use_peft=false")

@@ -146,6 +146,8 @@ def backward_fp32(model, st: StepState, on_ready=None):
             ft.wgrad32(dx, aos[l], "wo", l)
         ops.f32_attn_bwd(qkvs[l], dao, a["kstart"], dqkv, lse, delta, B, S, H, G, scale)
         ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
+        if geo.qk_norm:                                    # dqkv: gradient of the normed heads -> of the plain projection
+            ops.f32_qk_norm_bwd(dqkv, a["qkv_pres"][l], w["q_norm"], w["k_norm"], a["qk_rstds"][l], M, H, G)
         ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, LDQ, ws=ws)
         if ft is not None:
             ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)

@@ -471,7 +471,7 @@ extern "C" int tasu_f32_colsum(const float* x, int ld, float* out, int R, int C,
 
 extern "C" int tasu_f32_layernorm_bwd_params(const float* dy, int lddy, const float* x, int ldx, const float* mean, const float* rstd,
                                              float* dgamma, float* dbeta, int R, int D, void* stream) {
-  if (!dy || !x || !mean || !rstd || !dgamma || !dbeta || R <= 0 || D <= 0) return TASU_ERR_ARG;
+  if (!dy || !x || !mean || !rstd || !dgamma || !dbeta || R <= 0 || D <= 0 || lddy < D || ldx < D) return TASU_ERR_ARG;
   TASU_LAUNCH(layernorm_bwd_params_kernel, dim3((D + 255) / 256), dim3(256), 0, (hipStream_t)stream, dy, lddy, x, ldx, mean, rstd, dgamma,
               dbeta, R, D);
   return TASU_OK;
@@ -498,9 +498,11 @@ static int attn_bwd_launch(const float* qkv, const float* dout, const int32_t* k
   const int lds_kv = (2 * HD + 2 * REP * kst + 8 * HD) * 4;
   static bool set = false;
   if (!set) {                                         // (the attribute: the largest the kernels may ask for, S = MAXK)
-    (void)hipFuncSetAttribute((const void*)attn_bwd_q_kernel<REP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (2 * REP * HD + 2 * REP * MAXK + 4 * REP * HD + 4 * REP) * 4);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<REP>, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * HD + 2 * REP * MAXK + 8 * HD) * 4);
+    if (hipFuncSetAttribute((const void*)attn_bwd_q_kernel<REP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (2 * REP * HD + 2 * REP * MAXK + 4 * REP * HD + 4 * REP) * 4) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<REP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (2 * HD + 2 * REP * MAXK + 8 * HD) * 4) != hipSuccess)
+      return TASU_ERR_LAUNCH;                         // (as f32_ca.hip's launch: the flag is set only once both calls succeeded)
     set = true;
   }
   const unsigned grid = (unsigned)((long long)B * S * G);

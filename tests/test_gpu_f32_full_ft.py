@@ -98,8 +98,8 @@ def test_composed_route_meets_the_same_bound(ops):
 
 
 # ------------------------------------------------------------------------------------------ 2. tasu_f32_rmsnorm_wgrad, colsum
-@pytest.mark.parametrize("R,D", [(1, 256), (77, 512), (1024, 1536)])
-@pytest.mark.parametrize("given", [False, True])
+@pytest.mark.parametrize("R,D", [(1, 256), (77, 512), (1024, 1536), (5, 4), (130, 4), (5, 260), (130, 260)])   # D = 4: one lane of one
+@pytest.mark.parametrize("given", [False, True])                                                               # block; 260: a second block, one live lane
 def test_f32_rmsnorm_wgrad_against_float64(ops, R, D, given):
     """rstd recomputed from x and eps (what the step does) or passed in; the reference is float64 on the very inputs."""
     from ps_slm_amd.ops import RMS_WGRAD_SPLIT

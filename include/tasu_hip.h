@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TASU_ABI_VERSION 26
+#define TASU_ABI_VERSION 27
 int tasu_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------- GEMM
@@ -577,6 +577,26 @@ int tasu_qk_norm_bwd(void* dqkv, const void* pre, const float* wq, const float* 
                      void* stream);
 int tasu_qk_norm_rope_append(void* qkv, const float* wq, const float* wk, const float* cos_tab, const float* sin_tab, void* kcache,
                              void* vcache, const int32_t* pos, int M, int H, int G, int ctx, float eps, void* stream);
+/* The q_norm / k_norm weight gradients (full fine-tuning of a Qwen3 decoder), both arithmetics:
+ *   dwq[d] = or += sum over rows m and q heads h of g[m, h, d] * xn[m, h, d];  dwk: the same sum over the k heads
+ * with g = dqkv as the attention backward leaves it behind its RoPE backward (the gradient of w * xn: call this BEFORE
+ * tasu_qk_norm_bwd / tasu_f32_qk_norm_bwd overwrites dqkv in place), pre the plain projection and rstd [M, H+G] what the forward
+ * kept.  The v block is never read.
+ *   tasu_qk_norm_wgrad (bf16 dqkv / pre):      xn = bf16(pre * r), the operand the forward multiplied by w, rounding included; a
+ *           product of two bf16 values is exact in fp32, the sums are fp32.
+ *   tasu_f32_qk_norm_wgrad (fp32 dqkv / pre):  xn = pre * r in fp32: Qwen3RMSNorm's weight gradient on fp32 tensors.
+ * Two stages, no atomics, nothing depends on the device: TASU_QK_WGRAD_SPLIT workgroups for every shape, each walking the (row,
+ * head) units b * U + i, + TASU_QK_WGRAD_SPLIT * U, ... (U = 16 units per workgroup in the bf16 family, 8 in the fp32 family), a
+ * lane summing its own dims in that order, the workgroup's groups summed in group order into one slab [2, 128] of ws; a second
+ * launch sums the slabs in ascending order.  The same bits on every run and every device.
+ * TASU_ERR_ARG before any launch: a NULL pointer; dqkv, pre or ws not 16-byte aligned (rstd, dwq, dwk: 4-byte); H % G != 0 or a
+ * non-positive size; M * (H+2G) over the sibling kernels' limit (INT32_MAX / 16, / 32 in the fp32 family);
+ * ws_floats < TASU_QK_WGRAD_SPLIT * 256; dqkv == pre.                                                                            */
+#define TASU_QK_WGRAD_SPLIT 512
+int tasu_qk_norm_wgrad(const void* dqkv_bf16, const void* pre_bf16, const float* rstd, float* dwq, float* dwk, float* ws,
+                       int64_t ws_floats, int M, int H, int G, int accumulate, void* stream);
+int tasu_f32_qk_norm_wgrad(const float* dqkv, const float* pre, const float* rstd, float* dwq, float* dwk, float* ws, int64_t ws_floats,
+                           int M, int H, int G, int accumulate, void* stream);
 /* index[m, i] = (m / n_beams) * n_beams for i < S (shared prompt), m for i >= S. */
 int tasu_kv_index_init(int32_t* index, int B, int n_beams, int S, int ctx, void* stream);
 /* dst[m, :lens[m]] = src[src_row[m], :lens[m]] (src_row NULL = identity); dst != src; entries >= lens[m] untouched. */

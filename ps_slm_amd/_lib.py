@@ -89,6 +89,7 @@ PROTOTYPES = {
     "tasu_qk_norm_rope_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "tasu_qk_norm_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "tasu_qk_norm_rope_append": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "tasu_qk_norm_wgrad": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
     "tasu_kv_index_init": [vp, i32, i32, i32, i32, vp],
     "tasu_kv_index_reorder": [vp, vp, vp, vp, i32, i32, vp],
     "tasu_attn_decode": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
@@ -159,6 +160,7 @@ PROTOTYPES.update({
     "tasu_f32_rope": [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp],
     "tasu_f32_qk_norm_rope": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp],
     "tasu_f32_qk_norm_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "tasu_f32_qk_norm_wgrad": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
     "tasu_f32_gemm_qkv_norm_rope": [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, i64, vp],
     "tasu_f32_kv_fill": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "tasu_f32_attn_prefill": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
@@ -196,7 +198,7 @@ PROTOTYPES.update({
     "tasu_f32_colsum_split": [vp, i32, vp, vp, i32, i32, i32, vp],
 })
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 GEMM_SOURCES = ("common.h", "gemm_epilogue.h", "gemm_dispatch.h", "gemm.hip", "gemm_pipe.hip", "gemm_pp.hip")

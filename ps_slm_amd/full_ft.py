@@ -6,8 +6,10 @@ ps_slm_amd/lora.py plays for the adapters.
 Bucket (``TasuModel.proj``: p / g / m / v fp32 and pb, the bf16 image AdamW writes):
     [projector | model.norm | lm_head (untied only) | layer L-1 | ... | layer 0 | embedding table]
 every tensor starts on a multiple of 64 elements (the gaps hold zeros: zero gradient, zero value, AdamW leaves them zero).  A
-layer is [down | gate|up | post_attention_layernorm | o | q|k|v weight | q|k|v bias | input_layernorm] -- the order in which the
-backward completes them, layers last to first, so that ``grad_ranges()`` hands the engine contiguous ranges in completion order.
+layer is [down | gate|up | post_attention_layernorm | o | q|k|v weight | q|k|v bias | input_layernorm] -- on a Qwen3 geometry
+(``geo.qk_norm``) [down | gate|up | post_attention_layernorm | o | q_norm | k_norm | q|k|v weight | input_layernorm]: the two [128]
+head-norm weights where the backward completes them and no bias (qkv_bias is false: the zero bias LLMWeights keeps for its consumers
+stays frozen, outside the bucket and every state dict) -- the order in which the backward completes them, layers last to first, so that ``grad_ranges()`` hands the engine contiguous ranges in completion order.
 q|k|v and gate|up stay fused as the kernels read them; the reference's per-module names are row blocks of the fused tensors.  The
 embedding table goes last and IS the use_emb mechanism (TasuModel.enable_embedding_training: lookup term + the tied head's term).
 
@@ -17,7 +19,8 @@ transpose, the fragment-order decode copies and the decode graphs -- follows eve
 
 Weight gradients (fp32, straight into the bucket): dW = dY^T X by tasu_gemm_tn_bf16 from the row-major bf16 operands the step keeps
 (the normed inputs, the attention output, the SwiGLU output: per layer in this mode), the q|k|v bias by tasu_colsum_bf16_split of dqkv
-behind the RoPE backward, the norm weights by tasu_rmsnorm_wgrad from exactly what tasu_rmsnorm_bwd reads.  On the main stream,
+behind the RoPE backward, the norm weights by tasu_rmsnorm_wgrad from exactly what tasu_rmsnorm_bwd reads, Qwen3's q_norm / k_norm
+by tasu_qk_norm_wgrad (tasu_f32_qk_norm_wgrad on the fp32 step) from what tasu_qk_norm_bwd reads, before it overwrites dqkv.  On the main stream,
 next to the dgrad that consumes the same dY.
 
 On the fp32 training step (``arith_train == "fp32"``: use_fp16 = false) the bucket layout is the same, and the masters ARE the weights:
@@ -37,7 +40,8 @@ EMBED_KEY = PRE + "model.embed_tokens.weight"
 HEAD_KEY = PRE + "lm_head.weight"
 NORM_KEY = PRE + "model.norm.weight"
 LAYER_ORDER = ("wd", "wgu", "ln2", "wo", "wqkv", "bqkv", "ln1")     # completion order of one layer's gradients
-F32_TENSORS = ("ln1", "ln2")                                         # read from the fp32 masters; the others from the bf16 image
+QK_NORM_LAYER_ORDER = ("wd", "wgu", "ln2", "wo", "q_norm", "k_norm", "wqkv", "ln1")     # ... of a Qwen3 layer: head norms, no q|k|v bias
+F32_TENSORS = ("ln1", "ln2", "q_norm", "k_norm")                     # read from the fp32 masters; the others from the bf16 image
 
 
 def is_llm_key(k):
@@ -59,7 +63,11 @@ class LLMTrainables:
         if self.fp32 and V % 4:
             raise NotImplementedError(f"freeze_llm=false on the fp32 step: vocabulary size {V} must be a multiple of 4 (tasu_f32_gemm_tn)")
         Q, KV = H * HD, G * HD
-        self.shapes = {"wd": (D, I), "wgu": (2 * I, D), "ln2": (D,), "wo": (D, Q), "wqkv": (Q + 2 * KV, D), "bqkv": (Q + 2 * KV,), "ln1": (D,)}
+        # a Qwen3 layer (geo.qk_norm) carries the two head-norm weights where a Qwen2 layer carries the q|k|v bias; its zero bias
+        # stays a frozen tensor of LLMWeights, outside the bucket and every state dict
+        self.layer_order = QK_NORM_LAYER_ORDER if geo.qk_norm else LAYER_ORDER
+        self.shapes = {"wd": (D, I), "wgu": (2 * I, D), "ln2": (D,), "wo": (D, Q), "wqkv": (Q + 2 * KV, D), "bqkv": (Q + 2 * KV,), "ln1": (D,),
+                       "q_norm": (HD,), "k_norm": (HD,)}
         # reference module name -> (fused tensor, first row, rows)
         self.parts = {
             "input_layernorm.weight": ("ln1", 0, D), "post_attention_layernorm.weight": ("ln2", 0, D),
@@ -68,6 +76,9 @@ class LLMTrainables:
             "self_attn.o_proj.weight": ("wo", 0, D),
             "mlp.gate_proj.weight": ("wgu", 0, I), "mlp.up_proj.weight": ("wgu", I, I), "mlp.down_proj.weight": ("wd", 0, D),
         }
+        if geo.qk_norm:
+            self.parts = {k: v for k, v in self.parts.items() if v[0] != "bqkv"}
+            self.parts.update({"self_attn.q_norm.weight": ("q_norm", 0, HD), "self_attn.k_norm.weight": ("k_norm", 0, HD)})
         self.lo = pr.numel                                   # the projector's tensors end here (proj_end)
         off = rup(pr.numel, 64)
         self.offsets = {}                                    # (name, layer or None) -> (offset, shape)
@@ -84,7 +95,7 @@ class LLMTrainables:
         self.layer_range = [None] * L
         for l in range(L - 1, -1, -1):
             lo = off
-            for n in LAYER_ORDER:
+            for n in self.layer_order:
                 put((n, l), self.shapes[n])
             self.layer_range[l] = (lo, off)
         self.end = off
@@ -138,19 +149,20 @@ class LLMTrainables:
                 for mod, (n, r0, nr) in self.parts.items():
                     self.view(pr.p, n, l)[r0:r0 + nr].copy_(f(sd[f"{PRE}model.layers.{l}.{mod}"]))
             else:
-                for n in LAYER_ORDER:
+                for n in self.layer_order:
                     if w[n].data_ptr() != self.view(pr.p if n in F32_TENSORS else pr.pb, n, l).data_ptr():
                         src = f32w["layers"][l].get(n, w[n]) if f32w is not None else w[n]
                         if src.data_ptr() != self.view(pr.p, n, l).data_ptr():
                             self.view(pr.p, n, l).copy_(f(src))
-            for n in LAYER_ORDER:
+            for n in self.layer_order:
                 new = self.view(pr.p if n in F32_TENSORS else pr.pb, n, l)
                 if n in ("wqkv", "wo", "wgu", "wd") and w[n].data_ptr() != new.data_ptr():
                     llm._stale_ptrs.append(w[n].data_ptr())          # its fragment-order decode copy dies with it
                 w[n] = new
             if f32w is not None:
-                for n in ("wqkv", "bqkv", "wo", "wgu", "wd"):
-                    f32w["layers"][l][n] = self.view(pr.p, n, l)
+                for n in self.layer_order:
+                    if n not in ("ln1", "ln2"):                        # (the fp32 paths read the layer norms from LLMWeights.layers)
+                        f32w["layers"][l][n] = self.view(pr.p, n, l)
         norm = self.view(pr.p, "norm")
         if sd is not None:
             norm.copy_(f(sd[NORM_KEY]))
@@ -260,6 +272,16 @@ class LLMTrainables:
         m = self.model
         ws = m._buf("wgrad_rms_ws", (RMS_WGRAD_SPLIT * self.geo.llm_dim,), torch.float32)
         m.ops.rmsnorm_wgrad(dy, x, rstd, self.view(m.proj.g, name, layer), ws, src_rows=src_rows, accumulate=False)
+
+    def qk_wgrad(self, dqkv, pre, rstd, layer):
+        """g[q_norm], g[k_norm] of a Qwen3 layer = sum over rows and heads of dqkv * (pre * rstd), from what the head norm's backward
+        reads and BEFORE it overwrites dqkv (tasu_qk_norm_wgrad on the bf16 step, tasu_f32_qk_norm_wgrad on the fp32 step)."""
+        from .ops import QK_WGRAD_SPLIT
+        m, geo = self.model, self.geo
+        ws = m._buf("wgrad_qk_ws", (QK_WGRAD_SPLIT * 2 * HD,), torch.float32)
+        op = m.ops.f32_qk_norm_wgrad if self.fp32 else m.ops.qk_norm_wgrad
+        op(dqkv, pre, rstd, self.view(m.proj.g, "q_norm", layer), self.view(m.proj.g, "k_norm", layer), ws, dqkv.shape[0], geo.llm_heads,
+           geo.llm_kv_heads, accumulate=False)
 
     # ---- ... on the fp32 step (ps_slm_amd/train_fp32.py backward_fp32)
     def wgrad32(self, dy, x, name, layer=None, dst=None):

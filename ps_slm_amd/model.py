@@ -247,6 +247,14 @@ def f32_qk_norm_missing(ops):
     return tuple(n for n in F32_QK_NORM_OPS if not callable(getattr(type(ops), n, None)))
 
 
+def qk_norm_wgrad_missing(ops, arith_train="bf16"):
+    """The q_norm / k_norm weight-gradient operator (csrc/qk_norm.hip: full fine-tuning of a Qwen3 decoder) that the CLASS of an
+    operator set lacks for the given training arithmetic -- "qk_norm_wgrad" on the bf16 step, "f32_qk_norm_wgrad" on the fp32 step
+    -- or None; like f32_qk_norm_missing it touches no instance (``ops`` None: HipOps, which has both)."""
+    name = "f32_qk_norm_wgrad" if arith_train == "fp32" else "qk_norm_wgrad"
+    return None if ops is None or callable(getattr(type(ops), name, None)) else name
+
+
 class LLMWeights:
     """Frozen Qwen2 weights, bf16, fused and doubly laid out (see module docstring)."""
 
@@ -633,7 +641,10 @@ class TasuModel:
         if self.full_ft is not None:
             raise RuntimeError("the LLM is already trainable on this model")
         if self.geo.qk_norm:
-            raise NotImplementedError("freeze_llm=false on a qk_norm (Qwen3) decoder: the head norms' weight gradients are not built")
+            missing = qk_norm_wgrad_missing(self.ops, self.arith_train)
+            if missing:
+                raise NotImplementedError("freeze_llm=false on a qk_norm (Qwen3) decoder: this operator set has no weight gradient of "
+                                          f"the head norms (missing: {missing})")
         if self.lora is not None or self.embed_base is not None:
             raise RuntimeError("enable_llm_training with LoRA / use_emb: freeze_llm=false with use_peft=true is the LoRA recipe (peft freezes the base weights)")
         if self.arith_train == "fp32" and not self.f32_wgrad_served:
@@ -655,7 +666,9 @@ class TasuModel:
         from .full_ft import EMBED_KEY, HEAD_KEY, NORM_KEY, PRE
         geo = self.geo
         mods = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.o_proj.weight", "mlp.gate_proj.weight",
-                "mlp.up_proj.weight", "mlp.down_proj.weight") + tuple(f"self_attn.{m}_proj.{k}" for m in "qkv" for k in ("weight", "bias"))
+                "mlp.up_proj.weight", "mlp.down_proj.weight") + tuple(f"self_attn.{m}_proj.weight" for m in "qkv") + \
+            (tuple(f"self_attn.{m}_proj.bias" for m in "qkv") if geo.qkv_bias else ()) + \
+            (("self_attn.q_norm.weight", "self_attn.k_norm.weight") if geo.qk_norm else ())
         need = [f"{PRE}model.layers.{l}.{m}" for l in range(geo.llm_layers) for m in mods] + [NORM_KEY, EMBED_KEY] + ([] if geo.tied else [HEAD_KEY])
         lacking = [k for k in need if k not in sd]
         if lacking:

@@ -17,6 +17,7 @@ GEMM_BF16, GEMM_F32, GEMM_RESID = 0, 1, 2
 GEMM_WS_BYTES = (64 << 20) + 4096 * 4          # tasu_gemm_nt_bf16_ws workspace: counters + split-K partial tiles
 LN_BWD_SPLIT = 16
 RMS_WGRAD_SPLIT = 64                           # TASU_RMS_WGRAD_SPLIT: row slabs of tasu_rmsnorm_wgrad's workspace
+QK_WGRAD_SPLIT = 512                           # TASU_QK_WGRAD_SPLIT: slabs [2, 128] of tasu_qk_norm_wgrad's workspace
 
 
 class F32Fragments:
@@ -392,6 +393,12 @@ class HipOps:
     def qk_norm_bwd(self, dqkv, pre, wq, wk, rstd, M, H, G):
         """In place on dqkv (behind the attention backward's RoPE backward): the q/k head norm's backward; v block untouched."""
         self._chk(self.lib.tasu_qk_norm_bwd(_p(dqkv), _p(pre), _p(wq), _p(wk), _p(rstd), M, H, G, self._stream()), "tasu_qk_norm_bwd")
+
+    def qk_norm_wgrad(self, dqkv, pre, rstd, dwq, dwk, ws, M, H, G, accumulate=False):
+        """dwq / dwk [128] = or += sum over rows and q / k heads of dqkv * bf16(pre * rstd): the q_norm / k_norm weight gradients from
+        what qk_norm_bwd reads, BEFORE it overwrites dqkv (tasu_qk_norm_wgrad).  ``ws``: QK_WGRAD_SPLIT * 256 floats."""
+        self._chk(self.lib.tasu_qk_norm_wgrad(_p(dqkv), _p(pre), _p(rstd), _p(dwq), _p(dwk), _p(ws), 0 if ws is None else ws.numel(), M, H, G,
+                                              int(accumulate), self._stream()), "tasu_qk_norm_wgrad")
 
     def attn_fwd(self, qkv, vt, key_mask, out, lse, B, S, H, G, scale, causal):
         if self.attn_kernel["fwd"] != "policy":
@@ -885,6 +892,11 @@ class HipOps:
         """dqkv (the gradient of the normed heads, behind f32_rope(inverse=True)) -> the gradient of the plain projection, in place."""
         self._chk(self.lib.tasu_f32_qk_norm_bwd(_p(dqkv), _p(pre), _p(wq), _p(wk), _p(rstd), M, H, G, self._stream()),
                   "tasu_f32_qk_norm_bwd")
+
+    def f32_qk_norm_wgrad(self, dqkv, pre, rstd, dwq, dwk, ws, M, H, G, accumulate=False):
+        """qk_norm_wgrad on the fp32 operands of f32_qk_norm_bwd: xn = pre * rstd, nothing rounded to bf16 (tasu_f32_qk_norm_wgrad)."""
+        self._chk(self.lib.tasu_f32_qk_norm_wgrad(_p(dqkv), _p(pre), _p(rstd), _p(dwq), _p(dwk), _p(ws), 0 if ws is None else ws.numel(), M, H, G,
+                                                  int(accumulate), self._stream()), "tasu_f32_qk_norm_wgrad")
 
     def f32_rmsnorm(self, x, w, y, M, D, eps):
         self._chk(self.lib.tasu_f32_rmsnorm(_p(x), _p(w), _p(y), M, D, eps, self._stream()), "tasu_f32_rmsnorm")

@@ -218,7 +218,8 @@ def model_factory(train_config, model_config, **kwargs):
     for Qwen2 and Qwen3 decoders alike: true -> the bf16-autocast path, false (the reference's shipped scripts) -> the fp32 kernels
     for generate(), evaluation and, where train_fp32.py serves the recipe, the training step.  A Qwen3 decoder (per-head q/k
     RMSNorm) in fp32 needs an operator set whose class has f32_qk_norm_rope / f32_qk_norm_bwd / f32_gemm_qkv_norm_rope (HipOps
-    has them); with use_peft=true or freeze_llm=false it is refused on either path."""
+    has them); with freeze_llm=false it needs qk_norm_wgrad (bf16 step) / f32_qk_norm_wgrad (fp32 step); with use_peft=true it is
+    refused on either path."""
     projector = model_config.get("encoder_projector", "linear-silu")
     if projector == "q-former":
         # FINDING: the reference cannot run its q-former either.  EncoderProjectorQFormer.forward(x, atts) (projector.py:91-100)
@@ -320,8 +321,9 @@ def model_factory(train_config, model_config, **kwargs):
                                   "(ps-slm.py:515-523) calls the projector with one argument, EncoderProjectorCTCCA needs two")
     geo = geometry_from_config(model_config, raw_features=raw)
     if geo.qk_norm:
-        # Qwen3 (per-head q/k RMSNorm, csrc/qk_norm.hip): served with a frozen decoder on the bf16-autocast path and, for an operator
-        # set whose class has the fp32 head-norm operators (HipOps does), on the fp32 path; everything else is refused here, before
+        # Qwen3 (per-head q/k RMSNorm, csrc/qk_norm.hip): served on the bf16-autocast path and, for an operator set whose class has
+        # the fp32 head-norm operators (HipOps does), on the fp32 path; with freeze_llm=false for one whose class has the head norms'
+        # weight gradient in the training arithmetic; everything else is refused here, before
         # any weight is built or any device work starts (the probe reads the operator set's CLASS, never the instance)
         if fp32_mode:
             from ps_slm_amd.model import f32_qk_norm_missing
@@ -334,8 +336,13 @@ def model_factory(train_config, model_config, **kwargs):
             raise NotImplementedError("a Qwen3 decoder with train_config.use_peft=true: the LoRA route's K-extended q|k|v GEMM carries "
                                       "the RoPE epilogue and cannot take the head norm -- LoRA on Qwen3 is a follow-up; set use_peft=false")
         if full_ft:
-            raise NotImplementedError("a Qwen3 decoder with train_config.freeze_llm=false: full fine-tuning needs the q_norm / k_norm "
-                                      "weights' gradients and their place in the trainable bucket -- a follow-up; set freeze_llm=true")
+            from ps_slm_amd.model import qk_norm_wgrad_missing
+            f32_step = fp32_mode and f32_train_served and not str(device).startswith("cpu")
+            missing = qk_norm_wgrad_missing(kwargs.get("ops", None), "fp32" if f32_step else "bf16")
+            if missing:
+                raise NotImplementedError("a Qwen3 decoder with train_config.freeze_llm=false: this operator set has no weight gradient "
+                                          f"of the q_norm / k_norm weights (missing: {missing}); set freeze_llm=true, or use the HIP "
+                                          "operator set")
     geo.projector = projector
     geo.projector_ds_rate = int(model_config.get("encoder_projector_ds_rate", 1) or 1) if projector in ("linear", "cov1d-linear") else 1
     tokenizer = setup_tokenizer(train_config, model_config, geo, **kwargs)

@@ -300,10 +300,13 @@ def layer_bwd(model, st, l, b, lora=None, ft=None, drop=False, mlp=True):
     ops.attn_bwd_fused(d["qkv"][l], d["key_mask"], b.dao, d["ao"][l], d["lse"][l], b.delta, d["cos"], d["sin"], dqkv, b.dkp, b.dvp,
                        B, S, H, G, HD ** -0.5, True)
     if geo.qk_norm:                                        # dqkv: gradient of the normed heads -> of the plain projection
+        if ft is not None:                                 # the head norms' weight gradients read dqkv before it is overwritten
+            ft.qk_wgrad(dqkv, d["qkv_pre"][l], d["qk_rstd"][l], l)
         ops.qk_norm_bwd(dqkv, d["qkv_pre"][l], w["q_norm"], w["k_norm"], d["qk_rstd"][l], M, H, G)
     if ft is not None:
         ft.wgrad(dqkv, d["ft_xn"][2 * l], "wqkv", l)
-        ft.bias_wgrad(dqkv, "bqkv", l)                     # q|k|v bias: dqkv behind the RoPE backward
+        if geo.qkv_bias:
+            ft.bias_wgrad(dqkv, "bqkv", l)                 # q|k|v bias: dqkv behind the RoPE backward
     ops.gemm(dqkv, w["wqkv_t"], dn, M, D, LDQ)
     if ft is not None:
         ft.norm_wgrad(dn, x_in, rstd[2 * l], "ln1", l)

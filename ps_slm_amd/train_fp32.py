@@ -147,12 +147,15 @@ def backward_fp32(model, st: StepState, on_ready=None):
         ops.f32_attn_bwd(qkvs[l], dao, a["kstart"], dqkv, lse, delta, B, S, H, G, scale)
         ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
         if geo.qk_norm:                                    # dqkv: gradient of the normed heads -> of the plain projection
+            if ft is not None:                             # the head norms' weight gradients read dqkv before it is overwritten
+                ft.qk_wgrad(dqkv, a["qkv_pres"][l], a["qk_rstds"][l], l)
             ops.f32_qk_norm_bwd(dqkv, a["qkv_pres"][l], w["q_norm"], w["k_norm"], a["qk_rstds"][l], M, H, G)
         ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, LDQ, ws=ws)
         if ft is not None:
             ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
             ft.wgrad32(dqkv, xnb, "wqkv", l)
-            ft.bias_wgrad32(dqkv, "bqkv", l)                                          # q|k|v bias: dqkv behind the inverse RoPE
+            if geo.qkv_bias:
+                ft.bias_wgrad32(dqkv, "bqkv", l)                                      # q|k|v bias: dqkv behind the inverse RoPE
             ft.norm_wgrad32(dn, xs[2 * l], "ln1", l)
         if lo is not None and "qkv" in dict(lo.lp.groups):
             ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)

@@ -8,7 +8,8 @@ linear, cov1d-linear, and cross-attention through the fused tasu_f32_ca_attn ove
 residual stream, fp32 q|k|v / RoPE / attention / MLP on fp32 copies of the frozen Qwen2 weights (with use_peft: the merged
 W + s B A of ps_slm_amd.lora.merged_llm_f32, one accessor, weights_f32), an fp32 KV cache, fp32 logits, log-softmax and top-k -- csrc/fp32.hip through the C-ABI (``tasu_f32_*``).  prompt_pass_fp32
 is the only fp32 decoder forward: the eval forward, generate()'s prefill and, with its activations kept, the fp32 training step
-(ps_slm_amd/train_fp32.py) run it.  The beam search itself is the
+(ps_slm_amd/train_fp32.py) run it, and its layer, _layer_fp32, is the only fp32 decoder layer (the decode step's as well; an adapted
+training step hands it the adapter runner: the dependency runs one way, train_fp32 -> this module).  The beam search itself is the
 same device-side bookkeeping as the bf16 path's (``tasu_beam_update``, the cache row index, ``DeviceBeam``), and a generated
 position is one hipGraph replay.  Nothing is rounded to bf16; sums run in another order than the reference's CPU BLAS (fp32 MFMA,
 K ascending, K-range slabs added in ascending order: deterministic).  The audio branch runs the frozen SenseVoice encoder, the CTC
@@ -22,6 +23,8 @@ launch that sums the projection's K-range slabs (csrc/qk_norm.hip, csrc/fp32.hip
 
 HBM-bound like the bf16 step, on twice the bytes: 6.2 GB of fp32 weights per generated position at Qwen2.5-1.5B.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -133,40 +136,56 @@ def weights_f32(model):
     return model.llm.f32
 
 
-def _layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, cache=None, ctx=0, frag=None,
-                keep_gu=False, keep_qk=None):
-    """One decoder layer; in: xn = RMSNorm(x_in, ln1[l]); out: x_mid = x_in + attention, x_out = x_mid + MLP, xn = the NEXT norm of
-    x_out (ln1[l + 1], or the final norm).  Decode and eval pass one buffer three times; the training step passes its kept slices.
-    Every projection carries the row-wise kernel behind it in the launch that sums its K-range slabs (tasu_f32_gemm_qkv_rope,
-    _resid_rmsnorm, _swiglu): 9 launches per layer at <= 64 beam rows instead of 13.  ``keep_gu``: gate|up is kept in ``gu`` for
-    the backward, so it runs as its own GEMM and SwiGLU instead of the fused finisher.  A qk_norm geometry (Qwen3) takes
-    tasu_f32_gemm_qkv_norm_rope in the place of tasu_f32_gemm_qkv_rope -- the per-head q/k RMSNorm between the projection and the
-    rotation, in the same launch; ``keep_qk = (pre, rstd)`` (the training step): the plain projection and the heads' rstd are kept
-    for the backward, so the GEMM and the row kernel run as two launches."""
+def _layer_fp32(model, l, b, attend, lo=None, drop=False, cache=None, ctx=0, frag=None):
+    """One decoder layer, the only fp32 one.  ``b``, the buffers: in b.xn = RMSNorm(b.x_in, ln1[l]); out b.x_mid = x_in + attention,
+    b.x_out = x_mid + MLP, b.xn = the NEXT norm of x_out (ln1[l + 1], or the final norm); b.qkv, b.ao, b.gu, b.act, b.cos, b.sin, b.ws
+    and b.rows.  Decode and eval hand in one buffer three times; the training step hands in its kept slices and sets b.keep, with
+    b.qk = (pre, rstd) on a qk_norm geometry (Qwen3): the plain projection and the heads' rstd, which the head norm's backward reads.
+    Every Linear has one branch.  Where nothing stands between the projection and the row-wise kernel behind it, both are the ONE
+    launch that sums the GEMM's K-range slabs (tasu_f32_gemm_qkv_rope or, with the per-head q/k RMSNorm in front of the rotation,
+    _qkv_norm_rope; _resid_rmsnorm; _swiglu): 9 launches per layer at <= 64 beam rows instead of 13.  Else: base GEMM -> the adapters'
+    branches -> the row operator.  What stands between is a tensor kept for the backward (gate|up; pre) or ``lo``, the adapter
+    runner of the training step (train_fp32.LoraF32): training runs the adapters unmerged, y = W x + s B (A drop(x)), so with ``lo``
+    the layer reads the BASE fp32 weights and EVERY Linear is unfused, those of a group without an adapted member too."""
     ops, geo, llm = model.ops, model.geo, model.llm
     D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
-    f, w = weights_f32(model)["layers"][l], llm.layers[l]
+    f, w = (llm.f32 if lo is not None else weights_f32(model))["layers"][l], llm.layers[l]
     next_norm = llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm
-    kc_l, vc_l, slot = cache if cache is not None else (None, None, None)
-    if not geo.qk_norm:
-        ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, cos_t, sin_t, rows, H, G, D, ws, kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
-    elif keep_qk is None:
-        ops.f32_gemm_qkv_norm_rope(xn, f["wqkv"], None, qkv, f["q_norm"], f["k_norm"], cos_t, sin_t, rows, H, G, D, geo.rms_eps, ws,
-                                   kc=kc_l, vc=vc_l, slot=slot, ctx=ctx)
+    xn, qkv, act, rows, ws, eps, keep = b.xn, b.qkv, b.act, b.rows, b.ws, geo.rms_eps, b.keep
+    kv = dict(zip(("kc", "vc", "slot"), cache or (None, None, None)), ctx=ctx)
+
+    def linear(g, x, wt, y, N, K, **kw):                   # the unfused form
+        ops.f32_gemm(x, wt, y, rows, N, K, **kw, ws=ws)
+        if lo is not None:
+            lo.forward(l, g, x, y, rows, ws, drop)
+
+    if geo.qk_norm and (keep or lo is not None):
+        linear("qkv", xn, f["wqkv"], b.qk[0], (H + 2 * G) * HD, D)
+        ops.f32_qk_norm_rope(b.qk[0], f["q_norm"], f["k_norm"], b.cos, b.sin, qkv, b.qk[1], rows, H, G, eps, **kv)
+    elif geo.qk_norm:
+        ops.f32_gemm_qkv_norm_rope(xn, f["wqkv"], None, qkv, f["q_norm"], f["k_norm"], b.cos, b.sin, rows, H, G, D, eps, ws, **kv)
+    elif lo is not None:                                   # (the training step: no cache to fill)
+        linear("qkv", xn, f["wqkv"], qkv, (H + 2 * G) * HD, D, bias=f["bqkv"])
+        ops.f32_rope(qkv, b.cos, b.sin, rows, H, G)
     else:
-        pre, rstd = keep_qk
-        ops.f32_gemm(xn, f["wqkv"], pre, rows, (H + 2 * G) * HD, D, ws=ws)
-        ops.f32_qk_norm_rope(pre, f["q_norm"], f["k_norm"], cos_t, sin_t, qkv, rstd, rows, H, G, geo.rms_eps, kc=kc_l, vc=vc_l,
-                             slot=slot, ctx=ctx)
-    attend(l, qkv, ao)
-    ops.f32_gemm_resid_rmsnorm(ao, f["wo"], x_mid, w["ln2"], xn, rows, D, H * HD, geo.rms_eps, ws, resid=x_in)
+        ops.f32_gemm_qkv_rope(xn, f["wqkv"], f["bqkv"], qkv, b.cos, b.sin, rows, H, G, D, ws, **kv)
+    attend(l, qkv, b.ao)
+    if lo is None:
+        ops.f32_gemm_resid_rmsnorm(b.ao, f["wo"], b.x_mid, w["ln2"], xn, rows, D, H * HD, eps, ws, resid=b.x_in)
+    else:
+        linear("o", b.ao, f["wo"], b.x_mid, D, H * HD, resid=b.x_in)
+        ops.f32_rmsnorm(b.x_mid, w["ln2"], xn, rows, D, eps)
     wgu, wd = (f["wgu"], f["wd"]) if frag is None else (ops.f32_weight(frag["layers"][l]["wgu"], rows, ws), ops.f32_weight(frag["layers"][l]["wd"], rows, ws))
-    if keep_gu:
-        ops.f32_gemm(xn, wgu, gu, rows, 2 * I, D, ws=ws)
-        ops.f32_swiglu(gu, act, rows, I)
+    if lo is None and not keep:
+        ops.f32_gemm_swiglu(xn, wgu, b.gu, act, rows, I, D, ws)
     else:
-        ops.f32_gemm_swiglu(xn, wgu, gu, act, rows, I, D, ws)
-    ops.f32_gemm_resid_rmsnorm(act, wd, x_out, next_norm, xn, rows, D, I, geo.rms_eps, ws, resid=x_mid)
+        linear("gu", xn, wgu, b.gu, 2 * I, D)
+        ops.f32_swiglu(b.gu, act, rows, I)
+    if lo is None:
+        ops.f32_gemm_resid_rmsnorm(act, wd, b.x_out, next_norm, xn, rows, D, I, eps, ws, resid=b.x_mid)
+    else:
+        linear("down", act, wd, b.x_out, D, I, resid=b.x_mid)
+        ops.f32_rmsnorm(b.x_out, next_norm, xn, rows, D, eps)
 
 
 def _need_f32(model):
@@ -175,7 +194,7 @@ def _need_f32(model):
                            "(model_factory sets LLMWeights.keep_f32 before loading)")
 
 
-def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
+def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None, lo=None, drop=False):
     """The decoder over the merged prompt in fp32, the one fp32 decoder forward of the eval forward, generate()'s prefill and the
     training step: projector -> embedding merge -> 28 layers (causal attention; a batch's padding is on one side: left-padded
     prompts mask their first ``S - valid`` keys, right-padded training batches need no key mask under the causal one -- their padded
@@ -183,7 +202,8 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
     there).  ``keep`` (a dict: the training step): every layer's activations go to stacked buffers -- layer l reads xs[2l] and
     writes xs[2l + 1] and xs[2l + 2] -- gate|up runs unfused, and ``keep`` receives what backward_fp32 reads (xs, qkvs, aos, gus,
     cos, sin, kstart and the projector's, project_fp32; on a qk_norm geometry also qkv_pres and qk_rstds, the plain projections and
-    the heads' rstd).  Returns (xn0 = the final-normed hidden states [B * S, D], valid, left)."""
+    the heads' rstd).  ``lo``, ``drop`` (the training step of an adapted decoder, from forward_train_fp32): the adapter runner every
+    layer gets, and whether this step draws dropout masks.  Returns (xn0 = the final-normed hidden states [B * S, D], valid, left)."""
     ops, geo, llm = model.ops, model.geo, model.llm
     _need_f32(model)
     B, S = st.B, st.S
@@ -223,14 +243,11 @@ def prompt_pass_fp32(model, st: StepState, on_layer=None, keep=None):
             on_layer(l, qkv)
         ops.f32_attn_prefill(qkv, kstart_b, ao, B, S, H, G, scale)
 
-    layer = _layer_fp32
-    if keep is not None and model.lora is not None:        # the training step of an adapted decoder runs the adapters unmerged
-        from .train_fp32 import lora_layer_fp32 as layer
     ops.f32_rmsnorm(xs[0], llm.layers[0]["ln1"], xn0, M0, D, geo.rms_eps)
     for l in range(L):
-        kw = dict(keep_qk=(pres[l], rstds[l])) if pres is not None else {}
-        layer(model, l, xs[2 * l], xs[2 * l + 1], xs[2 * l + 2], xn0, qkvs[l], aos[l], gus[l], act0, M0, cos0, sin0, attend_prompt,
-                    ws, keep_gu=keep is not None, **kw)
+        b = SimpleNamespace(x_in=xs[2 * l], x_mid=xs[2 * l + 1], x_out=xs[2 * l + 2], xn=xn0, qkv=qkvs[l], ao=aos[l], gu=gus[l], act=act0,
+                            rows=M0, cos=cos0, sin=sin0, ws=ws, keep=keep is not None, qk=(pres[l], rstds[l]) if pres is not None else None)
+        _layer_fp32(model, l, b, attend_prompt, lo, drop)
     if keep is not None:
         keep.update(xs=xs, qkvs=qkvs, aos=aos, gus=gus, cos=cos0, sin=sin0, kstart=kstart_b)
         if pres is not None:
@@ -328,6 +345,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
     gu, act = buf("f32_gu", (M, 2 * I), f32), buf("f32_act", (M, I), f32)
     cos, sin = buf("dec_cos", (M, HD // 2), f32), buf("dec_sin", (M, HD // 2), f32)
     kcv, vcv = kc.view(L, M * ctx * W), vc.view(L, M * ctx * W)
+    bufs = SimpleNamespace(x_in=x, x_mid=x, x_out=x, xn=xn, qkv=qkv, ao=ao, gu=gu, act=act, rows=M, cos=cos, sin=sin, ws=ws, keep=False)
 
     def attend_cache(l, qkv_, ao_):
         ops.f32_attn_decode(qkv_, kcv[l], vcv[l], index, kstart, bs.next_lens, ao_, M, H, G, ctx, scale)
@@ -340,7 +358,7 @@ def beam_search_generate_fp32(model, st: StepState, num_beams=4, max_new_tokens=
         ops.rope_table(bs.next_pos, cos, sin, HD, geo.rope_theta)
         ops.f32_rmsnorm(x, llm.layers[0]["ln1"], xn, M, D, geo.rms_eps)
         for l in range(L):
-            _layer_fp32(model, l, x, x, x, xn, qkv, ao, gu, act, M, cos, sin, attend_cache, ws, cache=(kcv[l], vcv[l], bs.next_slot), ctx=ctx, frag=frag)
+            _layer_fp32(model, l, bufs, attend_cache, cache=(kcv[l], vcv[l], bs.next_slot), ctx=ctx, frag=frag)
         ops.f32_gemm(xn, head, logits, M, V, D, ws=ws)                                 # xn: the final norm, from the last layer's finisher
         topk_and_update(M, False)
 

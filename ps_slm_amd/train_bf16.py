@@ -1,5 +1,5 @@
 """The decoder part of the bf16 training step: embedding merge -> 28 x decoder layer -> final norm -> lm_head -> shifted CE, and its
-backward down to d(loss)/d(inputs_embeds) -- functions of (model, st), the way ps_slm_amd/train_fp32.py holds the fp32 step.
+backward down to d(loss)/d(inputs_embeds) -- functions of (model, st); ps_slm_amd/train_fp32.py holds the fp32 step the same way.
 TasuModel.forward_llm / backward_llm / _loss_on_labelled_rows / _head_wgrad delegate here.
 
 The layer is spelt ONCE: layer_fwd and layer_bwd serve every recipe through two optional collaborators.

@@ -20,10 +20,19 @@ use_peft + use_emb the embedding table's gradient (lookup term + the tied head's
 (ReLU backward by the kept outputs' mask, the conv as one GEMM over the k-frame rows) and cross-attention (dq over the whole
 embedding table: tasu_f32_ca_attn_bwd, then dW_q = dq^T post) -- and so does an adapted decoder (use_peft: LoraF32 below, the
 unmerged forward y = W x + s B (A drop(x)) and the adapters' gradients into the bucket's tail).
+
+The layer is spelt ONCE per direction, as ps_slm_amd/train_bf16.py spells the bf16 step's -- decode_fp32._layer_fp32 (decode's and
+eval's layer, handed the adapter runner) and layer_bwd below -- and serves every recipe through two optional collaborators that
+exclude each other: the adapter runner (LoraF32) and the full-fine-tuning hooks (``model.full_ft``).  The sums are order-dependent
+by design (K ascending, slabs in ascending order), so the ORDER of the launches and the buffer behind every argument fix the bits of
+the loss and the gradients: pinned per recipe on a CPU double by tests/test_f32_step_trace_cpu.py.
 """
+from types import SimpleNamespace
+
 import torch
 
 from .decode_fp32 import _gemm_ws, prompt_pass_fp32
+from .full_ft import f32_wgrad
 from .model import HD, StepState, rup
 
 
@@ -63,10 +72,11 @@ def forward_train_fp32(model, st: StepState):
     f32, i32 = torch.float32, torch.int32
     buf, d = model._buf, st.dev
     keep = {}
-    st.lora_drop = model.lora is not None and model.lora.drop_on(model.training)
+    lo = lora_f32(model) if model.lora is not None else None       # an adapted decoder trains with its adapters unmerged
+    st.lora_drop = lo is not None and model.lora.drop_on(model.training)
     if st.lora_drop:
         ops.rng_advance(model.lora.rng)        # new masks for this micro-step, as the bf16 step draws them (TasuModel.forward_llm)
-    xn, _, _ = prompt_pass_fp32(model, st, keep=keep)
+    xn, _, _ = prompt_pass_fp32(model, st, keep=keep, lo=lo, drop=st.lora_drop)
     # ---- loss head: logits for every position (pad columns zeroed once: the lm_head dgrad contracts over Vp), CE + its gradient
     logits = buf("f32t_logits", (M, rup(V, 64)), f32)
     ops.f32_gemm(xn, llm.f32["head"], logits, M, V, D, ws=_gemm_ws(model))
@@ -79,6 +89,64 @@ def forward_train_fp32(model, st: StepState):
     st.fp32 = True
 
 
+def _rebuilt(model, st, which, l=None):
+    """A weight gradient's operand that the step does not keep, rebuilt from what it keeps, for whichever collaborator wants it:
+    ``"norm"`` the final norm of xs[2L], ``"ln2"`` of xs[2l + 1], ``"ln1"`` of xs[2l]; ``"act"`` the SwiGLU of gus[l]."""
+    ops, geo, llm, a = model.ops, model.geo, model.llm, st.dev["f32t"]
+    if which == "act":
+        out = model._buf("f32t_lora_act", (st.M, geo.llm_inter), torch.float32)
+        ops.f32_swiglu(a["gus"][l], out, st.M, geo.llm_inter)
+        return out
+    x, w = (a["xs"][2 * geo.llm_layers], llm.norm) if which == "norm" else (a["xs"][2 * l + (which == "ln2")], llm.layers[l][which])
+    out = model._buf("f32t_lora_xn", (st.M, geo.llm_dim), torch.float32)
+    ops.f32_rmsnorm(x, w, out, st.M, geo.llm_dim, geo.rms_eps)
+    return out
+
+
+def layer_bwd(model, st, l, b, lo, ft, drop):
+    """Backward of one decoder layer: the dgrad chain from b.dx, the gradient of the layer's output, to that of its input (in b.dx),
+    and behind every base dgrad what the one collaborator that is set (backward_fp32) hangs there."""
+    ops, geo, a = model.ops, model.geo, st.dev["f32t"]
+    M, D, I, H, G = st.M, geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads
+    xs, ws, w, t = a["xs"], b.ws, model.llm.layers[l], b.wt["layers"][l]
+    dx, dn, dact, dgu, dao, dqkv = b.dx, b.dn, b.dact, b.dgu, b.dao, b.dqkv
+
+    def behind(g, dy, dx_base, name, which):
+        """Behind the dgrad dy -> dx_base of group ``g`` (Linear ``name``), on the group's input -- ``which`` of _rebuilt, None: the
+        kept attention output: ``lo``: the members' adapter backward, their dx added to dx_base; ``ft``: every weight gradient
+        next to the dgrad that consumes the same dY -- the Linear's, its bias', and the norm's in front of it."""
+        if ft is None and (lo is None or g not in lo.members):
+            return
+        x = a["aos"][l] if which is None else _rebuilt(model, st, which, l)
+        if lo is not None:
+            return lo.backward(l, g, x, dy, dx_base, M, ws, drop)
+        ft.wgrad32(dy, x, name, l)
+        if name == "wqkv" and geo.qkv_bias:
+            ft.bias_wgrad32(dy, "bqkv", l)                 # q|k|v bias: dqkv behind the inverse RoPE
+        if which in ("ln1", "ln2"):
+            ft.norm_wgrad32(dx_base, xs[2 * l + (which == "ln2")], which, l)
+
+    # MLP block: x_out = x_mid + down(swiglu(gate|up(norm(x_mid))))
+    ops.f32_gemm(dx, t["wd"], dact, M, I, D, ws=ws)
+    behind("down", dx, dact, "wd", "act")
+    ops.f32_swiglu_bwd(dact, a["gus"][l], dgu, M, I)
+    ops.f32_gemm(dgu, t["wgu"], dn, M, D, 2 * I, ws=ws)
+    behind("gu", dgu, dn, "wgu", "ln2")
+    ops.f32_rmsnorm_bwd(dn, xs[2 * l + 1], w["ln2"], dx, M, D, geo.rms_eps, True)
+    # attention block: x_mid = x_in + o(attention(rope(q|k|v(norm(x_in)))))
+    ops.f32_gemm(dx, t["wo"], dao, M, H * HD, D, ws=ws)
+    behind("o", dx, dao, "wo", None)
+    ops.f32_attn_bwd(a["qkvs"][l], dao, a["kstart"], dqkv, b.lse, b.delta, st.B, st.S, H, G, HD ** -0.5)
+    ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
+    if geo.qk_norm:                                        # dqkv: gradient of the normed heads -> of the plain projection
+        if ft is not None:                                 # the head norms' weight gradients read dqkv before it is overwritten
+            ft.qk_wgrad(dqkv, a["qkv_pres"][l], a["qk_rstds"][l], l)
+        ops.f32_qk_norm_bwd(dqkv, a["qkv_pres"][l], w["q_norm"], w["k_norm"], a["qk_rstds"][l], M, H, G)
+    ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, (H + 2 * G) * HD, ws=ws)
+    behind("qkv", dqkv, dn, "wqkv", "ln1")
+    ops.f32_rmsnorm_bwd(dn, xs[2 * l], w["ln1"], dx, M, D, geo.rms_eps, True)
+
+
 def backward_fp32(model, st: StepState, on_ready=None):
     """dgrad through the decoder and the weight gradients of everything that trains -- the projector, the adapters, the decoder's
     own tensors (freeze_llm = false), the embedding table -- into ``proj.g``, all fp32.  ``on_ready(lo, hi)``: the engine's
@@ -86,82 +154,35 @@ def backward_fp32(model, st: StepState, on_ready=None):
     ops, geo, llm, pr = model.ops, model.geo, model.llm, model.proj
     B, S, M = st.B, st.S, st.M
     D, I, H, G, V, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_vocab, geo.llm_layers
-    LDQ, Vp = (H + 2 * G) * HD, rup(V, 64)
-    scale = HD ** -0.5
-    f32 = torch.float32
-    buf, d = model._buf, st.dev
+    f32, buf, d = torch.float32, model._buf, st.dev
     a = d["f32t"]
-    xs, qkvs, aos, gus = a["xs"], a["qkvs"], a["aos"], a["gus"]
-    wt = _transposed_weights(model)
-    ws = _gemm_ws(model)
-    lo = lora_f32(model) if model.lora is not None else None
+    lo, ft = lora_f32(model) if model.lora is not None else None, model.full_ft
+    # the two collaborators exclude each other (enable_llm_training refuses a LoRA model: with use_peft the base weights stay frozen),
+    # so wherever both could want a group's rebuilt operand, one of them does
+    assert lo is None or ft is None
     drop = bool(getattr(st, "lora_drop", False))
-    ft = model.full_ft
     head_term = ft is not None or (model.embed_base is not None and geo.tied)   # dW of the lm_head: its own tensor, or the tied table's
-    rebuild = lo is not None or ft is not None or head_term
-    xnb, actb = (buf("f32t_lora_xn", (M, D), f32), buf("f32t_lora_act", (M, I), f32)) if rebuild else (None, None)
-    dx, dn = buf("f32t_dx", (M, D), f32), buf("f32t_dn", (M, D), f32)
-    dact, dgu = buf("f32t_dact", (M, I), f32), buf("f32t_dgu", (M, 2 * I), f32)
-    dao, dqkv = buf("f32t_dao", (M, H * HD), f32), buf("f32t_dqkv", (M, LDQ), f32)
-    lse, delta = buf("f32t_lse", (B * H * S,), f32), buf("f32t_delta", (B * H * S,), f32)
+    b = SimpleNamespace(wt=_transposed_weights(model), ws=_gemm_ws(model),
+                        dx=buf("f32t_dx", (M, D), f32), dn=buf("f32t_dn", (M, D), f32),          # dn: gradient wrt a normed activation
+                        dact=buf("f32t_dact", (M, I), f32), dgu=buf("f32t_dgu", (M, 2 * I), f32),
+                        dao=buf("f32t_dao", (M, H * HD), f32), dqkv=buf("f32t_dqkv", (M, (H + 2 * G) * HD), f32),
+                        lse=buf("f32t_lse", (B * H * S,), f32), delta=buf("f32t_delta", (B * H * S,), f32))
     # loss head
     if head_term:
         # dlogits^T xn over all rows (rows without a label hold zeros): the untied lm_head's gradient, or the head term of the tied
         # table's, which backward_embed's lookup term is added to
-        from .full_ft import f32_wgrad
-        ops.f32_rmsnorm(xs[2 * L], llm.norm, xnb, M, D, geo.rms_eps)
+        xn = _rebuilt(model, st, "norm")
         if ft is not None:
-            ft.wgrad32(a["dlogits"][:, :V], xnb, "head", dst=model.embed_view(pr.g) if geo.tied else None)
+            ft.wgrad32(a["dlogits"][:, :V], xn, "head", dst=model.embed_view(pr.g) if geo.tied else None)
         else:
-            f32_wgrad(model, a["dlogits"][:, :V], xnb, model.embed_view(pr.g))
-    ops.f32_gemm(a["dlogits"], wt["head"], dn, M, D, Vp, ws=ws)
+            f32_wgrad(model, a["dlogits"][:, :V], xn, model.embed_view(pr.g))
+    ops.f32_gemm(a["dlogits"], b.wt["head"], b.dn, M, D, rup(V, 64), ws=b.ws)
     if ft is not None:
-        ft.norm_wgrad32(dn, xs[2 * L], "norm", None)
-    ops.f32_rmsnorm_bwd(dn, xs[2 * L], llm.norm, dx, M, D, geo.rms_eps, False)
+        ft.norm_wgrad32(b.dn, a["xs"][2 * L], "norm", None)
+    ops.f32_rmsnorm_bwd(b.dn, a["xs"][2 * L], llm.norm, b.dx, M, D, geo.rms_eps, False)
     for l in range(L - 1, -1, -1):
-        w, t = llm.layers[l], wt["layers"][l]
-        # MLP block: x_out = x_mid + down(swiglu(gate|up(norm(x_mid))))
-        ops.f32_gemm(dx, t["wd"], dact, M, I, D, ws=ws)
-        if lo is not None and "down" in dict(lo.lp.groups):
-            ops.f32_swiglu(gus[l], actb, M, I)                                       # the down projection's input, rebuilt
-            lo.backward(l, "down", actb, dx, dact, M, ws, drop)
-        if ft is not None:                                                           # every weight gradient next to the dgrad of the same dY
-            ops.f32_swiglu(gus[l], actb, M, I)
-            ft.wgrad32(dx, actb, "wd", l)
-        ops.f32_swiglu_bwd(dact, gus[l], dgu, M, I)
-        ops.f32_gemm(dgu, t["wgu"], dn, M, D, 2 * I, ws=ws)
-        if ft is not None:
-            ops.f32_rmsnorm(xs[2 * l + 1], w["ln2"], xnb, M, D, geo.rms_eps)
-            ft.wgrad32(dgu, xnb, "wgu", l)
-            ft.norm_wgrad32(dn, xs[2 * l + 1], "ln2", l)
-        if lo is not None and "gu" in dict(lo.lp.groups):
-            ops.f32_rmsnorm(xs[2 * l + 1], w["ln2"], xnb, M, D, geo.rms_eps)
-            lo.backward(l, "gu", xnb, dgu, dn, M, ws, drop)
-        ops.f32_rmsnorm_bwd(dn, xs[2 * l + 1], w["ln2"], dx, M, D, geo.rms_eps, True)
-        # attention block: x_mid = x_in + o(attention(rope(q|k|v(norm(x_in)))))
-        ops.f32_gemm(dx, t["wo"], dao, M, H * HD, D, ws=ws)
-        if lo is not None:
-            lo.backward(l, "o", aos[l], dx, dao, M, ws, drop)
-        if ft is not None:
-            ft.wgrad32(dx, aos[l], "wo", l)
-        ops.f32_attn_bwd(qkvs[l], dao, a["kstart"], dqkv, lse, delta, B, S, H, G, scale)
-        ops.f32_rope(dqkv, a["cos"], a["sin"], M, H, G, inverse=True)
-        if geo.qk_norm:                                    # dqkv: gradient of the normed heads -> of the plain projection
-            if ft is not None:                             # the head norms' weight gradients read dqkv before it is overwritten
-                ft.qk_wgrad(dqkv, a["qkv_pres"][l], a["qk_rstds"][l], l)
-            ops.f32_qk_norm_bwd(dqkv, a["qkv_pres"][l], w["q_norm"], w["k_norm"], a["qk_rstds"][l], M, H, G)
-        ops.f32_gemm(dqkv, t["wqkv"], dn, M, D, LDQ, ws=ws)
-        if ft is not None:
-            ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
-            ft.wgrad32(dqkv, xnb, "wqkv", l)
-            if geo.qkv_bias:
-                ft.bias_wgrad32(dqkv, "bqkv", l)                                      # q|k|v bias: dqkv behind the inverse RoPE
-            ft.norm_wgrad32(dn, xs[2 * l], "ln1", l)
-        if lo is not None and "qkv" in dict(lo.lp.groups):
-            ops.f32_rmsnorm(xs[2 * l], w["ln1"], xnb, M, D, geo.rms_eps)
-            lo.backward(l, "qkv", xnb, dqkv, dn, M, ws, drop)
-        ops.f32_rmsnorm_bwd(dn, xs[2 * l], w["ln1"], dx, M, D, geo.rms_eps, True)
-    d["dx"] = dx
+        layer_bwd(model, st, l, b, lo, ft, drop)
+    d["dx"] = b.dx
     if model.embed_base is not None:           # the table's lookup term, on top of the head term (tied) or of zeros
         model.backward_embed(st)
     if model.freeze_projector:                 # (a frozen projector: the adapters' / the decoder's part of the bucket alone)
@@ -173,43 +194,38 @@ def backward_fp32(model, st: StepState, on_ready=None):
     Rap, Kp, Do = st.Rap, pr.Kp, pr.Do
     rows = d["audio_rows_pad"] if "audio_rows_pad" in d else model._pad_rows(st)
     dy2 = buf("f32t_dy2", (Rap, Do), f32)
-    ops.f32_gather_rows(dx, rows, dy2, Rap, Do)
+    ops.f32_gather_rows(b.dx, rows, dy2, Rap, Do)
 
-    def wgrad(dy, x, name, N, K, tag):
-        """g[name] [N, K] = dy^T x over the Rap rows (tasu_f32_gemm_nt contracts rows: both operands transposed)."""
-        dy_t, x_t = buf(f"f32t_{tag}_dy_t", (N, Rap), f32), buf(f"f32t_{tag}_x_t", (K, Rap), f32)
-        ops.f32_transpose(dy, dy_t, Rap, N, Rap)
-        ops.f32_transpose(x, x_t, Rap, K, Rap)
-        ops.f32_gemm(dy_t, x_t, pr.view(pr.g, name), N, K, Rap, ws=ws)
+    def wgrad(dy, x, name):                    # g[name] [N, K] = dy^T x over the Rap rows (a multiple of 64: the route pads nothing)
+        f32_wgrad(model, dy, x, pr.view(pr.g, name), route="composed")
 
-    def dgrad(dy, name, N, K, tag):
-        """dy [Rap, N] W[name] [N, K] -> [Rap, K]."""
+    def dgrad(dy, name, tag):                  # dy [Rap, N] W[name] [N, K] -> [Rap, K]
+        N, K = pr.view(pr.p, name).shape
         w_t, out = buf(f"f32t_{tag}_w_t", (K, N), f32), buf(f"f32t_{tag}_dx", (Rap, K), f32)
         ops.f32_transpose(pr.view(pr.p, name), w_t, N, K, N)
-        ops.f32_gemm(dy, w_t, out, Rap, K, N, ws=ws)
+        ops.f32_gemm(dy, w_t, out, Rap, K, N, ws=b.ws)
         return out
 
     if pr.is_ca:
         # dq of softmax(q E^T / sqrt(dh)) E over the whole embedding table, then dW_q = dq^T post
         dq = buf("f32t_ca_dq", (Rap, Do), f32)
         ops.f32_ca_attn_bwd(a["q"], llm.embed, a["out"], dy2, a["lse"], dq, Rap, geo.ca_heads, ws=a["ca_ws"])
-        wgrad(dq, d["post"], "W_q.weight", Do, Kp, "wq")
+        wgrad(dq, d["post"], "W_q.weight")
     elif pr.has_norm:
-        _projector_backward_linear_silu(model, st, dy2, ws)
+        _projector_backward_linear_silu(model, st, dy2, wgrad, dgrad)
     else:
         # linear: [k frames] -> Linear -> ReLU -> Linear;  cov1d-linear: Conv1d over the k-frame rows -> ReLU -> the same
-        Hb, K1 = pr.Hb, pr.kin * Kp
         ops.f32_colsum(dy2, pr.view(pr.g, pr.n_b2), Rap, Do)
-        wgrad(dy2, a["h"], pr.n_w2, Do, Hb, "w2")
-        dh = dgrad(dy2, pr.n_w2, Do, Hb, "w2")
+        wgrad(dy2, a["h"], pr.n_w2)
+        dh = dgrad(dy2, pr.n_w2, "w2")
         ops.f32_relu_bwd(a["h"], dh, dh)
-        ops.f32_colsum(dh, pr.view(pr.g, pr.n_b1), Rap, Hb)
-        wgrad(dh, a["x1"], pr.n_w1, Hb, K1, "w1")
+        ops.f32_colsum(dh, pr.view(pr.g, pr.n_b1), Rap, pr.Hb)
+        wgrad(dh, a["x1"], pr.n_w1)
         if pr.has_conv:
-            dc0 = dgrad(dh, pr.n_w1, Hb, Kp, "w1")
+            dc0 = dgrad(dh, pr.n_w1, "w1")
             ops.f32_relu_bwd(a["x1"], dc0, dc0)
             ops.f32_colsum(dc0, pr.view(pr.g, "conv1d.bias"), Rap, Kp)
-            wgrad(dc0, a["xcat"], "conv1d.weight", Kp, pr.k * Kp, "w0")
+            wgrad(dc0, a["xcat"], "conv1d.weight")
     if on_ready is not None:
         on_ready(0, pr.numel)
 
@@ -232,6 +248,7 @@ class LoraF32:
 
     def __init__(self, model):
         self.m, self.lp = model, model.lora
+        self.members = dict(self.lp.groups)                # adapted group -> its adapted members (train_bf16's runner has the same)
         self.rk = rup(self.lp.r, 32)
         self.version = -1
         self.w = {}
@@ -276,7 +293,7 @@ class LoraF32:
     def forward(self, l, gname, x, y, M, ws, drop):
         """y [M, nout of the group] (the base Linear's output, bias / residual included) += every member's low-rank branch."""
         lp, ops, W = self.lp, self.m.ops, self.weights()
-        for t in dict(lp.groups).get(gname, ()):
+        for t in self.members.get(gname, ()):
             (i, o), c0, w = lp.dims[t], lp.cols[t], W[(l, t)]
             us = self._us(t, M)[l]
             ops.f32_gemm(self._dropped(l, t, x, M, i, drop), w["sA"], us, M, lp.r, i, ws=ws)
@@ -284,9 +301,10 @@ class LoraF32:
 
     def backward(self, l, gname, x, dy, dx_base, M, ws, drop):
         """dy [M, nout of the group]; x: the group's (undropped) input [M, in]; dx_base [M, in] += every member's input gradient;
-        dA / dB of the members into the adapter tail of the bucket."""
+        dA / dB of the members into the adapter tail of the bucket: full_ft.f32_wgrad's composed route spelt out here, because the
+        members share dy_t (and x_t, where dropout gives them no input of their own): the helper per member would add launches."""
         lp, m, ops, W = self.lp, self.m, self.m.ops, self.weights()
-        targets = dict(lp.groups).get(gname, ())
+        targets = self.members.get(gname, ())
         if not targets:
             return
         f32, r, rk, Mp = torch.float32, lp.r, self.rk, rup(M, 32)
@@ -325,54 +343,16 @@ def lora_f32(model):
     return run
 
 
-def lora_layer_fp32(model, l, x_in, x_mid, x_out, xn, qkv, ao, gu, act, rows, cos_t, sin_t, attend, ws, keep_gu=True):
-    """decode_fp32._layer_fp32 for the training step of an adapted decoder: the same layer on the BASE fp32 weights with every
-    adapted Linear's low-rank branch added before the operator behind it (RoPE, the residual's RMSNorm, SwiGLU), unfused."""
-    ops, geo, llm = model.ops, model.geo, model.llm
-    D, I, H, G, L = geo.llm_dim, geo.llm_inter, geo.llm_heads, geo.llm_kv_heads, geo.llm_layers
-    f, w = llm.f32["layers"][l], llm.layers[l]
-    lo = lora_f32(model)
-    drop = lo.lp.drop_on(model.training)
-    LDQ = (H + 2 * G) * HD
-    ops.f32_gemm(xn, f["wqkv"], qkv, rows, LDQ, D, bias=f["bqkv"], ws=ws)
-    lo.forward(l, "qkv", xn, qkv, rows, ws, drop)
-    ops.f32_rope(qkv, cos_t, sin_t, rows, H, G)
-    attend(l, qkv, ao)
-    ops.f32_gemm(ao, f["wo"], x_mid, rows, D, H * HD, resid=x_in, ws=ws)
-    lo.forward(l, "o", ao, x_mid, rows, ws, drop)
-    ops.f32_rmsnorm(x_mid, w["ln2"], xn, rows, D, geo.rms_eps)
-    ops.f32_gemm(xn, f["wgu"], gu, rows, 2 * I, D, ws=ws)
-    lo.forward(l, "gu", xn, gu, rows, ws, drop)
-    ops.f32_swiglu(gu, act, rows, I)
-    ops.f32_gemm(act, f["wd"], x_out, rows, D, I, resid=x_mid, ws=ws)
-    lo.forward(l, "down", act, x_out, rows, ws, drop)
-    ops.f32_rmsnorm(x_out, llm.layers[l + 1]["ln1"] if l + 1 < L else llm.norm, xn, rows, D, geo.rms_eps)
-
-
-def _projector_backward_linear_silu(model, st, dy2, ws):
-    """LayerNorm -> Linear -> SiLU -> Linear (the shipped projector) from the output rows' gradient dy2."""
-    ops, pr = model.ops, model.proj
-    f32 = torch.float32
-    buf, d = model._buf, st.dev
+def _projector_backward_linear_silu(model, st, dy2, wgrad, dgrad):
+    """LayerNorm -> Linear -> SiLU -> Linear (the shipped projector) from the output rows' gradient dy2; ``wgrad`` / ``dgrad``:
+    backward_fp32's helpers for a Linear of the projector."""
+    ops, pr, d = model.ops, model.proj, st.dev
     a = d["f32t"]
-    Rap, K, Kp, Hb, Do = st.Rap, pr.K, pr.Kp, pr.Hb, pr.Do
-    ops.f32_colsum(dy2, pr.view(pr.g, pr.n_b2), Rap, Do)
-    dy2_t, h_t = buf("f32t_dy2_t", (Do, Rap), f32), buf("f32t_h_t", (Hb, Rap), f32)
-    ops.f32_transpose(dy2, dy2_t, Rap, Do, Rap)
-    ops.f32_transpose(a["h"], h_t, Rap, Hb, Rap)
-    ops.f32_gemm(dy2_t, h_t, pr.view(pr.g, pr.n_w2), Do, Hb, Rap, ws=ws)                    # dW2 = dy2^T h
-    w2_t = buf("f32t_w2_t", (Hb, Do), f32)
-    ops.f32_transpose(pr.view(pr.p, pr.n_w2), w2_t, Do, Hb, Do)
-    dh = buf("f32t_dh", (Rap, Hb), f32)
-    ops.f32_gemm(dy2, w2_t, dh, Rap, Hb, Do, ws=ws)
+    ops.f32_colsum(dy2, pr.view(pr.g, pr.n_b2), st.Rap, pr.Do)
+    wgrad(dy2, a["h"], pr.n_w2)                                                              # dW2 = dy2^T h
+    dh = dgrad(dy2, pr.n_w2, "w2")
     ops.f32_silu(a["h_pre"], dh, dy=dh)                                                      # dh_pre, in place
-    ops.f32_colsum(dh, pr.view(pr.g, pr.n_b1), Rap, Hb)
-    dh_t, xn_t = buf("f32t_dh_t", (Hb, Rap), f32), buf("f32t_xn_t", (Kp, Rap), f32)
-    ops.f32_transpose(dh, dh_t, Rap, Hb, Rap)
-    ops.f32_transpose(a["xn_p"], xn_t, Rap, Kp, Rap)
-    ops.f32_gemm(dh_t, xn_t, pr.view(pr.g, pr.n_w1), Hb, Kp, Rap, ws=ws)                     # dW1 = dh_pre^T xn
-    w1_t = buf("f32t_w1_t", (Kp, Hb), f32)
-    ops.f32_transpose(pr.view(pr.p, pr.n_w1), w1_t, Hb, Kp, Hb)
-    dxn = buf("f32t_dxn", (Rap, Kp), f32)
-    ops.f32_gemm(dh, w1_t, dxn, Rap, Kp, Hb, ws=ws)
-    ops.f32_layernorm_bwd_params(dxn, d["post"], a["mean"], a["rstd"], pr.view(pr.g, "norm.weight"), pr.view(pr.g, "norm.bias"), Rap, K)
+    ops.f32_colsum(dh, pr.view(pr.g, pr.n_b1), st.Rap, pr.Hb)
+    wgrad(dh, a["xn_p"], pr.n_w1)                                                            # dW1 = dh_pre^T xn
+    dxn = dgrad(dh, pr.n_w1, "w1")
+    ops.f32_layernorm_bwd_params(dxn, d["post"], a["mean"], a["rstd"], pr.view(pr.g, "norm.weight"), pr.view(pr.g, "norm.bias"), st.Rap, pr.K)

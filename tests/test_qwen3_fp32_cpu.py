@@ -145,7 +145,10 @@ def test_fp32_layer_set_carries_the_head_norms():
 
 def test_fp32_layer_on_the_double_matches_the_restatement():
     """decode_fp32._layer_fp32's choice of operator, on the CPU double: a qk_norm geometry calls f32_gemm_qkv_norm_rope with the
-    layer's q_norm / k_norm and no bias, or -- keep_qk -- the plain GEMM and the row operator, with the same result"""
+    layer's q_norm / k_norm and no bias, or -- the training step's kept (pre, rstd) -- the plain GEMM and the row operator, with the
+    same result"""
+    from types import SimpleNamespace
+
     from ps_slm_amd import decode_fp32
 
     class Rec(Qwen3F32FakeOps):
@@ -181,9 +184,10 @@ def test_fp32_layer_on_the_double_matches_the_restatement():
     outs = []
     for keep in (None, (torch.zeros(rows, LDQ), torch.zeros(rows, H + G))):
         qkv, m.ops.seen = torch.zeros(rows, LDQ), []
+        b = SimpleNamespace(x_in=None, x_mid=None, x_out=None, xn=xn, qkv=qkv, ao=None, gu=None, act=None, rows=rows, cos=ang.cos(),
+                            sin=ang.sin(), ws=None, keep=keep is not None, qk=keep)
         with pytest.raises(StopIteration):
-            decode_fp32._layer_fp32(m, 1, None, None, None, xn, qkv, None, None, None, rows, ang.cos(), ang.sin(), lambda *a: None, None,
-                                    **({} if keep is None else dict(keep_qk=keep)))
+            decode_fp32._layer_fp32(m, 1, b, lambda *a: None)
         assert m.ops.seen == (["f32_gemm_qkv_norm_rope", "f32_qk_norm_rope"] if keep is None else ["f32_gemm", "f32_qk_norm_rope"])
         outs.append(qkv)
     assert torch.equal(outs[0], outs[1]) and float(outs[0].abs().max()) > 0
